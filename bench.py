@@ -17,10 +17,17 @@ With N GPUs (torchrun, one process per GPU) the job is N x steps x batch
 transfers sharded contiguously by transaction (zkatdlog.dist.verify_shard,
 weak scaling: each rank verifies steps x batch); the only collective is the
 verdict-bitmap all-gather over RCCL (configs[3]).  Prints ONE JSON line (a
-compact summary, < 6 KB) and writes every leg in full to --detail-out
-(gpurun_out/bench_detail.json).
+compact summary, < 6 KB).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run does only what the headline needs: set-up, warm-up, the timed
+steps, the result line.  --full adds every other leg (device-only rate,
+roofline, owner signatures, token requests, standalone MSMs, the batch prover,
+PP-B, the n=1 seam, the CPU baselines; each can be switched off with its own
+--no-* option) and writes every leg in full to --detail-out.
+--dump-outputs DIR writes what the timed call returned for its last step (the
+verdict codes of the job's last --batch transfers) to DIR/verdict_codes.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
 """
 import os as _os
 
@@ -819,6 +826,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4096, help="transfers per step (per GPU)")
     ap.add_argument("--distinct", type=int, default=16384, help="distinct GPU-made proofs in the workload")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline (CPU baselines, MSMs, prover, PP-B, seam, device-only, roofline, "
+                         "owner signatures, token requests) and the detail file; without it only the timed steps run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the verdict codes the timed call returned for its last step to DIR/verdict_codes.npy "
+                         "(float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--msm", default="16,20,24", help="log2 sizes of the standalone G1 MSM (configs[2]); '' = none")
     ap.add_argument("--no-prover", action="store_true", help="skip the batch-prover leg (configs[4])")
@@ -840,6 +853,9 @@ def main():
     ap.add_argument("--layout", default=os.environ.get("FTZ_LAYOUT", ""),
                     help="kernel layouts, e.g. 'g2lines=sextet,pairing=one_lane' (ftz_ctx_set_layout)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_prover = args.no_seam = args.no_ppb = args.no_extras = True
+        args.msm = ""
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -908,6 +924,12 @@ def main():
         ok_local = bool(np.array_equal(codes, job.expect[start:stop]))
         verdict_ok, n_accept = ok_local, int((codes == 0).sum())
 
+    if args.dump_outputs:  # what the caller of the timed path received for the last step of this rank's shard
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "verdict_codes" if world == 1 else "verdict_codes_rank%d" % rank
+        last = np.asarray(codes[-min(args.batch, 1 << 23):], dtype=np.float32)  # at most 32 MB
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), last)
+
     msm_split = None
     if dist is not None and args.msm:
         lg_split = 20 if "20" in args.msm.split(",") else int(args.msm.split(",")[-1])
@@ -973,14 +995,16 @@ def main():
             "msm_2^20_latency_ms": msm20, "msm": msm, "msm_resident": msm_res, "msm_split": msm_split, "prover": prover, "pp_b": ppb,
         }
         line.update(extras)
-        # every leg in full -> the detail file; the one stdout line (the driver
-        # keeps an 8 KB tail) is the compact summary of the same numbers
-        detail = os.path.join(ROOT, args.detail_out)
-        os.makedirs(os.path.dirname(detail), exist_ok=True)
-        with open(detail, "w") as f:
-            json.dump(line, f, indent=1)
         summary = compact_line(line)
-        summary["detail"] = args.detail_out
+        if args.full:
+            # every leg in full -> the detail file; the one stdout line (kept
+            # short for callers that read only the tail of the output) is the
+            # compact summary of the same numbers
+            detail = os.path.join(ROOT, args.detail_out)
+            os.makedirs(os.path.dirname(detail), exist_ok=True)
+            with open(detail, "w") as f:
+                json.dump(line, f, indent=1)
+            summary["detail"] = args.detail_out
         print(json.dumps(summary), flush=True)
     ctx.close()
     if dist is not None:

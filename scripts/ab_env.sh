@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-ARGS=${BENCH_ARGS:---steps 20 --warmup 2 --no-cpu-baseline --no-prover --msm 20}
+ARGS=${BENCH_ARGS:---full --steps 20 --warmup 2 --no-cpu-baseline --no-prover --msm 20}
 IFS='|' read -ra SETS <<< "${AB:-}"
 i=0
 for s in "${SETS[@]}"; do

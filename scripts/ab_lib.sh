@@ -8,7 +8,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-ARGS=${BENCH_ARGS:---steps 64 --warmup 2 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb}
+ARGS=${BENCH_ARGS:---full --steps 64 --warmup 2 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb}
 IFS='|' read -ra SETS <<< "${LIBS:-}"
 for r in $(seq 1 "${ROUNDS:-2}"); do
   for s in "${SETS[@]}"; do

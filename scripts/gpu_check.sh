@@ -20,6 +20,7 @@ if [ "${SMOKE:-1}" = 1 ]; then
   tail -2 gpurun_out/smoke.log
 fi
 if [ "${BENCH:-1}" = 1 ]; then
+  BENCH_ARGS=${BENCH_ARGS:---full}  # every leg, as before the headline-only default; BENCH_ARGS replaces it
   timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1 || { echo "bench failed"; tail -30 gpurun_out/bench.log; exit 5; }
   tail -c 3000 gpurun_out/bench.log
 fi

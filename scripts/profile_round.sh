@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 TAG=${TAG:-r02}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-BENCH="bench.py --steps 10 --warmup 1 --no-cpu-baseline --no-prover --msm 20,24 --distinct 4096"
+BENCH="bench.py --full --steps 10 --warmup 1 --no-cpu-baseline --no-prover --msm 20,24 --distinct 4096"
 SHORT="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-prover --msm 20 --no-extras --distinct 4096"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o k -- python3 $BENCH > $OUT/trace.log 2>&1 || { echo "trace run failed"; tail -20 $OUT/trace.log; exit 4; }
 tail -c 600 $OUT/trace.log

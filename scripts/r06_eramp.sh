@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb"
 for r in 1 2 3; do
   for v in r1024 r2048 noramp; do
     case $v in

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb"
 L="--lib $PWD/fabric-token-sdk_amd/zkatdlog/_lib/ab/libftsamd_ramp2.so"
 for r in 1 2 3 4; do
   for v in default r2_1024; do

@@ -8,7 +8,7 @@ timeout -k 10 120 python3 -u fabric-token-sdk_amd/tools/invbench.py > gpurun_out
 cat gpurun_out/r06i2_bench.log
 timeout -k 10 600 python -u -m pytest tests/test_gpu.py tests/test_gpu_engine.py tests/test_msm.py -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/r06i2_tests.log 2>&1 || { echo "tests failed"; tail -30 gpurun_out/r06i2_tests.log; exit 4; }
 tail -1 gpurun_out/r06i2_tests.log
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-prover --msm=20 --no-ppb"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-prover --msm=20 --no-ppb"
 for r in 1 2; do
   for v in sg30 sg62; do
     lib=""; [ $v = sg62 ] && lib="--lib $PWD/fabric-token-sdk_amd/zkatdlog/_lib/ab/libftsamd_sg62.so"

@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-BASE=${BASE_ARGS:---steps 256 --warmup 3 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb}
+BASE=${BASE_ARGS:---full --steps 256 --warmup 3 --no-cpu-baseline --no-prover --msm= --no-seam --no-ppb}
 IFS='|' read -ra SETS <<< "${SETS:-}"
 for r in $(seq 1 "${ROUNDS:-1}"); do
   i=0
