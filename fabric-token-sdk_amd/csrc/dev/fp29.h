@@ -329,17 +329,31 @@ FTS_HD int32_t f29_bdigit(int64_t acc) {
   return (int32_t)(((uint32_t)acc + (uint32_t)F29_HALF) & (uint32_t)F29_MASK) - F29_HALF;
 }
 
-// ca a + cb b - q p, balanced (|result| <= p/2 + e).  |ca|, |cb| <= 16 and
-// inputs with |limb| <= 2^29: every term fits the 64-bit sweep.
+// q = round(t8 2^232 / p) for t8 the limb-8 sum of a linear combination
+// V = sum c_k x_k (t8 = sum c_k x_k.l[8], any int32): one v_mad_i64_i32 against
+// the fixed-point reciprocal P29_QMUL = round(2^284 / p) < 2^31 and a shift of
+// the high word.  Distance to V / p, for |x_k limb| <= 2^29 and sum |c_k| <= 256:
+//   the limbs below 8 move V by at most sum |c_k| 2^232 (1 + 2^-28) <= 2^240.01,
+//     i.e. V / p by < 2^-13.5 (p > 2^253.5);
+//   |P29_QMUL - 2^284 / p| <= 1/2 moves t8 P29_QMUL / 2^52 by <= 2^-22;
+// so q = round(V / p + d) with |d| < 2^-13.4 and |V - q p| <= (1/2 + 2^-13.4) p:
+// the e of the balanced form's |value| <= p/2 + e (every consumer takes
+// 0.52 p).  For V = k p exactly (the zero tests on reduced values) q = k.
+FTS_HD int32_t f29_quot(int32_t t8) {
+  return (int32_t)(((int64_t)t8 * P29_QMUL + ((int64_t)1 << 51)) >> 52);
+}
+
+// ca a + cb b - q p, balanced (|result| <= p/2 + e, e < 2^-13.4 p: f29_quot).
+// |ca|, |cb| <= 16 and inputs with |limb| <= 2^29 (limb 8: |value| <= 32 p, the
+// f29_from_fp outputs of f29_breduce, is < 2^27): every term fits the 64-bit
+// sweep and the limb-8 sum an int32.
 FTS_HD f29 f29_lin2(const f29& a_, int32_t ca, const f29& b_, int32_t cb) {
   if (!__builtin_constant_p(ca)) ca = pin32(ca);
   if (!__builtin_constant_p(cb)) cb = pin32(cb);
   f29 a = a_, b = b_;  // limbs as 32-bit values here (not sign-extended copies from elsewhere)
   pin29(a);
   pin29(b);
-  double t = (double)ca * ((double)a.l[8] * 536870912.0 + (double)a.l[7]) +
-             (double)cb * ((double)b.l[8] * 536870912.0 + (double)b.l[7]);
-  const int32_t q = (int32_t)__builtin_rint(t * P29_TOP_INV);
+  const int32_t q = f29_quot(ca * a.l[8] + cb * b.l[8]);
   f29 r;
   int64_t acc = 0;
 #pragma unroll
@@ -359,11 +373,11 @@ FTS_HD f29 f29_lin2(const f29& a_, int32_t ca, const f29& b_, int32_t cb) {
 // ca a + cb b without the quotient: one balanced carry sweep (limbs 0..7 in
 // [-2^28, 2^28), limb 8 the signed rest), the value unchanged -- for operands
 // that are only ever multiplied (|value| <= (|ca| + |cb|)(p/2 + e) stays far
-// inside the product's value budget, and the limbs inside its column budget)
-FTS_HD f29 f29_lin2_ns(const f29& a_, int32_t ca, const f29& b_, int32_t cb) {
-  f29 a = a_, b = b_;
-  pin29(a);
-  pin29(b);
+// inside the product's value budget, and the limbs inside its column budget).
+// The caller pins a and b (pin29) once for all the sweeps it runs on them:
+// pinned copies made here cost one v_mov_b32 per limb and sweep whenever the
+// operand stays live (36 per published value, with xi a's two sweeps).
+FTS_HD f29 f29_lin2_ns(const f29& a, int32_t ca, const f29& b, int32_t cb) {
   f29 r;
   int64_t acc = 0;
 #pragma unroll
@@ -379,8 +393,9 @@ FTS_HD f29 f29_lin2_ns(const f29& a_, int32_t ca, const f29& b_, int32_t cb) {
   return r;
 }
 
-// c0 x0 + c1 x1 + c2 x2 + c3 x3 - q p, balanced (|result| <= p/2 + e); |c_i|
-// <= 64 and balanced inputs (|limb| <= 2^29)
+// c0 x0 + c1 x1 + c2 x2 + c3 x3 - q p, balanced (|result| <= p/2 + e, e as
+// f29_lin2's); |c_i| <= 64 and balanced inputs (|limb| <= 2^29, |limb 8| < 2^22:
+// the limb-8 sum stays inside an int32)
 FTS_HD f29 f29_lin4(const f29& x0_, int32_t c0, const f29& x1_, int32_t c1, const f29& x2_, int32_t c2,
                     const f29& x3_, int32_t c3) {
   f29 x0 = x0_, x1 = x1_, x2 = x2_, x3 = x3_;
@@ -392,11 +407,7 @@ FTS_HD f29 f29_lin4(const f29& x0_, int32_t c0, const f29& x1_, int32_t c1, cons
   c1 = pin32(c1);
   c2 = pin32(c2);
   c3 = pin32(c3);
-  double t = (double)c0 * ((double)x0.l[8] * 536870912.0 + (double)x0.l[7]) +
-             (double)c1 * ((double)x1.l[8] * 536870912.0 + (double)x1.l[7]) +
-             (double)c2 * ((double)x2.l[8] * 536870912.0 + (double)x2.l[7]) +
-             (double)c3 * ((double)x3.l[8] * 536870912.0 + (double)x3.l[7]);
-  const int32_t q = (int32_t)__builtin_rint(t * P29_TOP_INV);
+  const int32_t q = f29_quot(c0 * x0.l[8] + c1 * x1.l[8] + c2 * x2.l[8] + c3 * x3.l[8]);
   f29 r;
   int64_t acc = 0;
 #pragma unroll
@@ -432,7 +443,8 @@ FTS_HD q2 q2_sel(bool c, const q2& a, const q2& b) {
 }
 // xi a = (9 a0 - a1) + (a0 + 9 a1) u, reduced
 FTS_HD q2 q2_mul_xi(const q2& a) { return {f29_lin2(a.c0, 9, a.c1, -1), f29_lin2(a.c0, 1, a.c1, 9)}; }
-// the same value carry-swept only (|value| <= 5 p + e): a multiplicand
+// the same value carry-swept only (|value| <= 10 |a|): a multiplicand; a pinned
+// by the caller (f29_lin2_ns)
 FTS_HD q2 q2_mul_xi_lazy(const q2& a) { return {f29_lin2_ns(a.c0, 9, a.c1, -1), f29_lin2_ns(a.c0, 1, a.c1, 9)}; }
 FTS_HD q2 q2_add(const q2& a, const q2& b) { return {f29_add(a.c0, b.c0), f29_add(a.c1, b.c1)}; }
 

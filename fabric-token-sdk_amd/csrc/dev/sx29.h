@@ -49,8 +49,12 @@ FTS_HD void w29_init(W29& w) {
 #pragma unroll
   for (int i = 0; i < 17; i++) w.u[i] = w.v[i] = w.w[i] = 0;
 }
-// w += a b (a, b balanced, or limbs within 2^29)
-FTS_HD void w29_mac(W29& w, const q2& a, const q2& b) {
+// w += a b (a, b balanced, or limbs within 2^29).  FIRST: w = a b, the rows
+// holding nothing yet -- the first limb product of a column (i = 0 or j = 8)
+// writes it, a MAD with a zero addend, so the first term of a sum needs no
+// zeroed rows (w29_init: 51 v_mov_b64 per sum)
+template <bool FIRST>
+FTS_HD void w29_mac_t(W29& w, const q2& a, const q2& b) {
   FTS_COUNT_MAD(192);  // the 32-bit equivalent (3 wide products), for opcounts
   FTS_SCHED_FENCE();
   const f29 sa = f29_add(a.c0, a.c1), sb = f29_add(b.c0, b.c1);
@@ -58,11 +62,14 @@ FTS_HD void w29_mac(W29& w, const q2& a, const q2& b) {
   for (int i = 0; i < 9; i++)
 #pragma unroll
     for (int j = 0; j < 9; j++) {
-      w.u[i + j] += w29_p(a.c0.l[i], b.c0.l[j]);
-      w.v[i + j] += w29_p(a.c1.l[i], b.c1.l[j]);
-      w.w[i + j] += w29_p(sa.l[i], sb.l[j]);
+      const bool set = FIRST && (i == 0 || j == 8);
+      w.u[i + j] = (set ? 0 : w.u[i + j]) + w29_p(a.c0.l[i], b.c0.l[j]);
+      w.v[i + j] = (set ? 0 : w.v[i + j]) + w29_p(a.c1.l[i], b.c1.l[j]);
+      w.w[i + j] = (set ? 0 : w.w[i + j]) + w29_p(sa.l[i], sb.l[j]);
     }
 }
+FTS_HD void w29_mac(W29& w, const q2& a, const q2& b) { w29_mac_t<false>(w, a, b); }
+FTS_HD void w29_set(W29& w, const q2& a, const q2& b) { w29_mac_t<true>(w, a, b); }
 // row += x^2: cross products once with the doubled operand (|2 x_i| < 2^31)
 FTS_HD void w29_row_sqr(uint64_t r[17], const f29& x) {
 #pragma unroll
@@ -89,8 +96,9 @@ FTS_HD void w29_init(W29& w) {
 #pragma unroll
   for (int i = 0; i < 17; i++) w.re[i] = w.im[i] = 0;
 }
-// w += a b (a, b balanced)
-FTS_HD void w29_mac(W29& w, const q2& a, const q2& b) {
+// w += a b (a, b balanced); FIRST: w = a b, no zeroed rows (see above)
+template <bool FIRST>
+FTS_HD void w29_mac_t(W29& w, const q2& a, const q2& b) {
   FTS_COUNT_MAD(192);  // the 32-bit equivalent (3 wide products), for opcounts
   FTS_SCHED_FENCE();
   f29 nb1 = f29_neg(b.c1);
@@ -98,15 +106,22 @@ FTS_HD void w29_mac(W29& w, const q2& a, const q2& b) {
   for (int i = 0; i < 9; i++)
 #pragma unroll
     for (int j = 0; j < 9; j++) {
-      w.re[i + j] += (int64_t)a.c0.l[i] * b.c0.l[j];
+      const bool set = FIRST && (i == 0 || j == 8);
+      w.re[i + j] = (set ? 0 : w.re[i + j]) + (int64_t)a.c0.l[i] * b.c0.l[j];
       w.re[i + j] += (int64_t)a.c1.l[i] * nb1.l[j];
-      w.im[i + j] += (int64_t)a.c0.l[i] * b.c1.l[j];
+      w.im[i + j] = (set ? 0 : w.im[i + j]) + (int64_t)a.c0.l[i] * b.c1.l[j];
       w.im[i + j] += (int64_t)a.c1.l[i] * b.c0.l[j];
     }
 }
+FTS_HD void w29_mac(W29& w, const q2& a, const q2& b) { w29_mac_t<false>(w, a, b); }
+FTS_HD void w29_set(W29& w, const q2& a, const q2& b) { w29_mac_t<true>(w, a, b); }
 #endif
-// Montgomery reduction of one row, balanced digits and result
-FTS_HD f29 w29_redc(int64_t c[17]) {
+// Montgomery reduction of one row, balanced digits and result.  ADD: the value
+// row / R + f, f's limbs joining columns 9..17 (R f) ahead of the tail sweep --
+// limbs 0..7 of the sum come out balanced, limb 8 takes the signed rest
+// (|f limb| <= 2^29 adds nothing to the column budget: 2^29 against 2^56)
+template <bool ADD>
+FTS_HD f29 w29_redc_t(int64_t c[17], const f29& f) {
   FTS_COUNT_MAD(72);
 #pragma unroll
   for (int k = 0; k < 9; k++) {
@@ -121,13 +136,15 @@ FTS_HD f29 w29_redc(int64_t c[17]) {
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     acc += c[9 + i];
+    if (ADD) acc += f.l[i];
     const int32_t lo = f29_bdigit(acc);
     r.l[i] = lo;
     acc = (acc + F29_HALF) >> 29;  // = (acc - lo) / 2^29: lo is acc's balanced low digit
   }
-  r.l[8] = (int32_t)acc;
+  r.l[8] = (int32_t)acc + (ADD ? f.l[8] : 0);
   return r;
 }
+FTS_HD f29 w29_redc(int64_t c[17]) { return w29_redc_t<false>(c, f29{}); }
 #if FTS_SX_KARA
 FTS_HD q2 w29_reduce(W29& w) {
   int64_t re[17], im[17];
@@ -138,8 +155,21 @@ FTS_HD q2 w29_reduce(W29& w) {
   }
   return {w29_redc(re), w29_redc(im)};
 }
+// w / R + f (w29_redc_t<true>)
+FTS_HD q2 w29_reduce_add(W29& w, const q2& f) {
+  int64_t re[17], im[17];
+#pragma unroll
+  for (int i = 0; i < 17; i++) {
+    re[i] = (int64_t)(w.u[i] - w.v[i]);
+    im[i] = (int64_t)(w.w[i] - (w.u[i] + w.v[i]));
+  }
+  return {w29_redc_t<true>(re, f.c0), w29_redc_t<true>(im, f.c1)};
+}
 #else
 FTS_HD q2 w29_reduce(W29& w) { return {w29_redc(w.re), w29_redc(w.im)}; }
+FTS_HD q2 w29_reduce_add(W29& w, const q2& f) {
+  return {w29_redc_t<true>(w.re, f.c0), w29_redc_t<true>(w.im, f.c1)};
+}
 // w += s^2 (s balanced) as (s0 + s1)(s0 - s1) + 2 s0 s1 u: two limb-product rows
 // instead of the four of w29_mac(w, s, s)
 FTS_HD void w29_sqr_acc(W29& w, const q2& s) {
@@ -184,8 +214,7 @@ FTS_HD q2 w29_prod1(const q2& a, const q2& b) {
 
 FTS_HD q2 q2_mul(const q2& a, const q2& b) {
   W29 w;
-  w29_init(w);
-  w29_mac(w, a, b);
+  w29_set(w, a, b);
   return w29_reduce(w);
 }
 
@@ -225,10 +254,17 @@ struct Sq {
   }
 };
 
+// Publishes v and xi v.  v is pinned once here for xi v's two sweeps
+// (f29_lin2_ns) and returned: a caller that uses v afterwards continues with
+// the returned value, so that no register copy of v is made for the pin.
 template <class X>
-FTS_HD void sq_pub(const X& x, int base, const q2& v) {
+FTS_HD q2 sq_pub(const X& x, int base, const q2& v_) {
+  q2 v = v_;
+  pin29(v.c0);
+  pin29(v.c1);
   x.put(base + x.k, v);
   x.put(base + 6 + x.k, q2_mul_xi_lazy(v));  // xi v is only ever a multiplicand
+  return v;
 }
 
 // c = a * b, b published in SX_B / SX_BX (as sx_mul)
@@ -237,9 +273,11 @@ FTS_HD q2 sq_mul(X x, q2 a) {
   x.put(SX_A + x.k, a);
   x.sync();
   W29 w;
-  w29_init(w);
+  // the term i = 5 writes the rows (peeling the last term keeps the loop's
+  // addressing that of the full loop; peeling the first added 14 VALU per turn)
+  w29_set(w, x.get(SX_A + 5), x.get(x.k < 5 ? X::BX + x.k + 1 : X::B));
 #pragma nounroll
-  for (int i = 0; i < 6; i++) {
+  for (int i = 0; i < 5; i++) {
     int j = x.k - i;
     int sb = j < 0 ? X::BX + j + 6 : X::B + j;
     w29_mac(w, x.get(SX_A + i), x.get(sb));
@@ -273,7 +311,7 @@ template <class X>
 FTS_HD q2 sq_cyc_sqr(X x, q2 a) {
   const int k = x.k, odd = k & 1;
   const int p = odd ? (k == 3 ? 0 : (k == 5 ? 1 : 2)) : (k >> 1);
-  sq_pub(x, SX_A, a);
+  a = sq_pub(x, SX_A, a);
   x.sync();
   q2 u = x.get(SX_A + p), v = x.get(SX_A + p + 3), xv = x.get(SX_AX + p + 3);
   q2 s = q2_sel(odd, u, q2_add(u, v)), t = q2_sel(odd, v, q2_add(u, xv));
@@ -299,7 +337,7 @@ FTS_HD q2 sq_cyc_sqr(X x, q2 a) {
 template <class X>
 FTS_HD q2 sq_cyc_sqr(X x, q2 a) {
   const int k = x.k, m = k >> 1;
-  sq_pub(x, SX_A, a);
+  a = sq_pub(x, SX_A, a);
   x.sync();
   bool odd = (k & 1) != 0;
   int i1 = odd ? (k == 1 ? 5 : (k == 3 ? 3 : 4)) : m + 3;
@@ -646,13 +684,16 @@ template <class X>
 FTS_HD q2 sq_sqr(X x, q2 a) {
   const int k = x.k;
   const bool odd = (k & 1) != 0;
-  sq_pub(x, SX_A, a);
+  a = sq_pub(x, SX_A, a);
   x.put(SX_A2 + k, {f29_add(a.c0, a.c0), f29_add(a.c1, a.c1)});
   x.sync();
   W29 w;
-  w29_init(w);
+  {
+    uint32_t e = term_at(SX_SQR4_TAB[odd ? 0 : 1], k);
+    w29_set(w, x.get(e & 63), x.get((e >> 6) & 63));
+  }
 #pragma nounroll
-  for (int t = 0; t < 3; t++) {
+  for (int t = 1; t < 3; t++) {
     uint32_t e = term_at(SX_SQR4_TAB[odd ? t : t + 1], k);
     w29_mac(w, x.get(e & 63), x.get((e >> 6) & 63));
   }
@@ -667,12 +708,12 @@ FTS_HD q2 sq_mul_line_r(const X& x, const q2& f, const q2& l0, const q2& l1, con
   sq_pub(x, SX_A, f);
   x.sync();
   W29 w;
-  w29_init(w);
+  w29_set(w, l0, x.get(SX_A + x.k));  // the l0 term writes the rows
 #pragma nounroll
-  for (int t = 0; t < 3; t++) {
-    int j = x.k - (t == 0 ? 0 : (t == 1 ? 1 : 3));
+  for (int t = 1; t < 3; t++) {
+    int j = x.k - (t == 1 ? 1 : 3);
     int sb = j < 0 ? SX_AX + j + 6 : SX_A + j;
-    w29_mac(w, t == 0 ? l0 : (t == 1 ? l1 : l3), x.get(sb));
+    w29_mac(w, t == 1 ? l1 : l3, x.get(sb));
   }
   x.sync();
   return w29_reduce(w);
@@ -690,10 +731,10 @@ FTS_HD q2 sq_mul_evline(const X& x, const q2& f, const EvLineDev* l2, uint32_t s
   sq_pub(x, SX_A, f);
   x.sync();
   W29 w;
-  w29_init(w);
+  w29_set(w, evline_ld29(l2, s, 0, idx, njobs), x.get(SX_A + x.k));
 #pragma nounroll
-  for (int t = 0; t < 3; t++) {
-    int j = x.k - (t == 0 ? 0 : (t == 1 ? 1 : 3));
+  for (int t = 1; t < 3; t++) {
+    int j = x.k - (t == 1 ? 1 : 3);
     int sb = j < 0 ? SX_AX + j + 6 : SX_A + j;
     w29_mac(w, evline_ld29(l2, s, t, idx, njobs), x.get(sb));
   }
@@ -727,6 +768,46 @@ FTS_HD q2 sq_fixed_line(const X& x, const q2& f, const LineCoef29& q, const f29&
 // yi = 1/yP come from the G1 combine (g1_pnorm).  Lanes 0..3 form the four
 // Fp products; f + f (l1 w + l3 w^3) then costs two limb-product pairs per
 // lane instead of sq_fixed_line's three.
+//
+// sq_fixed_line_sum: f + f (l1 w + l3 w^3) for f published in SX_A / SX_AX, the
+// sum formed inside the reduction (w29_reduce_add: (row + R f) / R), so f + r
+// costs eight column adds per row instead of a quotient-estimate sweep.  The
+// result g is NOT reduced; bounds, in units of p with p / R < 1 / 168.9:
+//   r: a lane sums two Fp2 products (four field products per component) of a
+//     line coefficient (|l| <= 0.52) and f_j or, wrapped, xi f_j (<= 10 |f|):
+//     |r| <= 1/2 + 4 x 0.52 x 10 |f| / 168.9 = 1/2 + 0.123 |f|, so
+//     |g| <= 1.123 |f| + 1/2;
+//   limbs 0..7 of g are balanced (the tail sweep), limb 8 holds the rest:
+//     |g| <= 3 means |limb 8| < 2^24, and xi g (<= 30, published by the
+//     carry-swept q2_mul_xi_lazy) |limb 8| < 2^27 -- inside the 2^28 every
+//     column bound assumes.
+// Consumers either multiply g (sq_pub, then a product) or square it:
+//   verifier chain (sq_miller_fn): sq_sqr out <= 1/2 + 102 a^2 / 168.9 (lane
+//     0: a0^2 + xi (2 a1 a5 + 2 a2 a4 + a3^2), 51 Fp2 products of |a|^2), the
+//     line product out <= 1/2 + 2 x 0.52 (1 + 10 + 10) |g| / 168.9 = 1/2 +
+//     0.129 |g|.  With line out m <= 0.68: sq_sqr out <= 0.78, g <= 1.38, and
+//     the next line out <= 0.678 -- the bounds close, the chain ends on m;
+//   prover chain (sq_miller_f3n): three lines in a row from <= 0.78 reach
+//     1.38, 2.05, 2.80; the loop then reduces (f29_breduce) before the next
+//     squaring, which at 2.8 would not contract (102 x 2.8^2 / 168.9 = 4.7).
+template <class X>
+FTS_HD q2 sq_fixed_line_sum(const X& x, const q2& f, const q2& l1, const q2& l3) {
+  const int k = x.k;
+  W29 w;
+  // zeroed rows and a rolled two-term loop: with the first term writing the
+  // rows both products sit in one block, and k_miller_n then needs 256 VGPRs
+  // and 12 bytes of scratch per lane, k_miller_f3 132 (none this way)
+  w29_init(w);
+#pragma nounroll
+  for (int t = 0; t < 2; t++) {
+    int j = k - (t == 0 ? 1 : 3);
+    int sb = j < 0 ? SX_AX + j + 6 : SX_A + j;
+    w29_mac(w, t == 0 ? l1 : l3, x.get(sb));
+  }
+  x.sync();
+  return w29_reduce_add(w, f);
+}
+
 template <class X>
 FTS_HD q2 sq_fixed_line_n(const X& x, const q2& f, const LineCoef29& q, const f29& xq, const f29& yi, bool inf) {
   const int k = x.k;
@@ -738,24 +819,14 @@ FTS_HD q2 sq_fixed_line_n(const X& x, const q2& f, const LineCoef29& q, const f2
   x.sync();
   q2 l1 = {x.get(SX_P + 0).c0, x.get(SX_P + 1).c0};
   q2 l3 = {x.get(SX_P + 2).c0, x.get(SX_P + 3).c0};
-  sq_pub(x, SX_A, f);
+  const q2 fp = sq_pub(x, SX_A, f);
   x.sync();
-  W29 w;
-  w29_init(w);
-#pragma nounroll
-  for (int t = 0; t < 2; t++) {
-    int j = k - (t == 0 ? 1 : 3);
-    int sb = j < 0 ? SX_AX + j + 6 : SX_A + j;
-    w29_mac(w, t == 0 ? l1 : l3, x.get(sb));
-  }
-  x.sync();
-  q2 r = w29_reduce(w);
-  q2 g = {f29_lin2(f.c0, 1, r.c0, 1), f29_lin2(f.c1, 1, r.c1, 1)};
-  return q2_sel(inf, f, g);
+  return q2_sel(inf, fp, sq_fixed_line_sum(x, fp, l1, l3));
 }
 
 // sq_fixed_line_n with the lane's multiplicand v already selected (lanes 0, 1:
-// xP/yP, lanes 2, 3: 1/yP; lanes 4, 5: anything)
+// xP/yP, lanes 2, 3: 1/yP; lanes 4, 5: anything).  The result is unreduced
+// (sq_fixed_line_sum); the caller reduces after at most three lines in a row.
 template <class X>
 FTS_HD q2 sq_fixed_line_nv(const X& x, const q2& f, const LineCoef29& q, const f29& v, bool inf) {
   const int k = x.k;
@@ -767,20 +838,11 @@ FTS_HD q2 sq_fixed_line_nv(const X& x, const q2& f, const LineCoef29& q, const f
   x.sync();
   q2 l1 = {x.get(SX_P + 0).c0, x.get(SX_P + 1).c0};
   q2 l3 = {x.get(SX_P + 2).c0, x.get(SX_P + 3).c0};
+  // f itself, not the pinned value sq_pub returns: continuing with that one
+  // costs k_miller_f3 60 bytes of scratch per lane (256 VGPRs)
   sq_pub(x, SX_A, f);
   x.sync();
-  W29 w;
-  w29_init(w);
-#pragma nounroll
-  for (int t = 0; t < 2; t++) {
-    int j = k - (t == 0 ? 1 : 3);
-    int sb = j < 0 ? SX_AX + j + 6 : SX_A + j;
-    w29_mac(w, t == 0 ? l1 : l3, x.get(sb));
-  }
-  x.sync();
-  q2 r = w29_reduce(w);
-  q2 g = {f29_lin2(f.c0, 1, r.c0, 1), f29_lin2(f.c1, 1, r.c1, 1)};
-  return q2_sel(inf, f, g);
+  return q2_sel(inf, f, sq_fixed_line_sum(x, f, l1, l3));
 }
 
 // the lane's multiplicand of a normalised fixed line at P (pn = (xP/yP, 1/yP))
@@ -813,6 +875,7 @@ FTS_HD q2 sq_miller_f3n(const X& x, const LineCoef29* l0, const LineCoef29* l1, 
       for (int i = 0; i < 9; i++) v.l[i] = t == 0 ? v0.l[i] : (t == 1 ? v1.l[i] : v2.l[i]);
       f = sq_fixed_line_nv(x, f, L[s], v, t == 0 ? inf0 : (t == 1 ? inf1 : inf2));
     }
+    f = {f29_breduce(f.c0), f29_breduce(f.c1)};  // |f| <= 2.8 p after three unreduced line sums
   }
   return f;
 }

@@ -1,0 +1,265 @@
+// TEST-ONLY stand-alone driver (own main) for the pairing side's limb
+// primitives of dev/fp29.h and dev/sx29.h at the edges of their contracts:
+//   lin2 / lin4   f29_lin2 / f29_lin4 with the integer quotient estimate,
+//   prod          a sum of Fp2 products whose first term writes the rows
+//                 (w29_set, then w29_mac) against zeroed rows (w29_init),
+//   fline         the fixed line's fused sum (w29_reduce_add: row / R + f)
+//                 against the plain reduction of the same rows.
+// Inputs: every limb at +-2^28 (and +-2^29 where the contract allows it), the
+// signs that make every limb product of a column positive, values at +-(p/2),
+// multiples of p, coefficient corners, and random balanced values.  Every case
+// is printed as one line of integers; tests/test_sx_bounds.py recomputes it
+// with big integers mod p and checks the limb and value bounds.  Built a
+// second time with -fsanitize=undefined,signed-integer-overflow, a signed
+// column overflow aborts the run.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "../../fabric-token-sdk_amd/csrc/dev/jobs.h"
+#include "../../fabric-token-sdk_amd/csrc/dev/sx29.h"
+
+using namespace fts;
+
+namespace {
+
+uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+uint64_t rnd() {
+  rng_state ^= rng_state << 13;
+  rng_state ^= rng_state >> 7;
+  rng_state ^= rng_state << 17;
+  return rng_state;
+}
+int32_t rnd_in(int32_t lo, int32_t hi) { return lo + (int32_t)(rnd() % (uint64_t)((int64_t)hi - lo + 1)); }
+
+const int32_t B28 = 1 << 28;
+const int32_t TOP_HALF = 3171406 / 2 + 1;  // limb 8 of a value of p/2
+
+// random balanced element: limbs 0..7 in [-2^28, 2^28), |value| <= ~p/2
+f29 rnd_bal() {
+  f29 r;
+  for (int i = 0; i < 8; i++) r.l[i] = rnd_in(-B28, B28 - 1);
+  r.l[8] = rnd_in(-(TOP_HALF - 1), TOP_HALF - 1);
+  return r;
+}
+// every limb 0..7 = s_i lim (sign pattern bits), limb 8 = top
+f29 corner(int32_t lim, uint32_t signs, int32_t top) {
+  f29 r;
+  for (int i = 0; i < 8; i++) r.l[i] = ((signs >> i) & 1) ? -lim : lim;
+  r.l[8] = top;
+  return r;
+}
+// +-(p - 1) / 2 in balanced limbs
+f29 half_p(bool neg) {
+  uint32_t h[9];
+  uint32_t carry = 0;
+  for (int i = 8; i >= 0; i--) {  // (p - 1) >> 1 over the unsigned 29-bit limbs (p odd: drop the low bit)
+    uint32_t v = (uint32_t)P29[i] | (carry << 29);
+    h[i] = v >> 1;
+    carry = v & 1;
+  }
+  f29 r;
+  int32_t c = 0;
+  for (int i = 0; i < 8; i++) {
+    int32_t t = (int32_t)h[i] + c;
+    int32_t lo = ((t + B28) & F29_MASK) - B28;
+    r.l[i] = lo;
+    c = (t - lo) >> 29;
+  }
+  r.l[8] = (int32_t)h[8] + c;
+  return neg ? f29_neg(r) : r;
+}
+// k p in (unbalanced) limbs, |k| <= 2: limbs within 2^29
+f29 mult_p(int32_t k) {
+  f29 r;
+  for (int i = 0; i < 9; i++) r.l[i] = k * P29B[i];
+  return r;
+}
+
+void put(const f29& a) {
+  for (int i = 0; i < 9; i++) printf(" %d", a.l[i]);
+}
+void put(const q2& a) {
+  put(a.c0);
+  put(a.c1);
+}
+
+// contract: 1 = inputs are values the kernels can hold (the value bound is checked too)
+void lin2(const f29& a, int32_t ca, const f29& b, int32_t cb, int contract) {
+  printf("lin2 %d %d %d", contract, ca, cb);
+  put(a);
+  put(b);
+  put(f29_lin2(a, ca, b, cb));
+  printf("\n");
+}
+void lin4(const f29 x[4], const int32_t c[4], int contract) {
+  printf("lin4 %d %d %d %d %d", contract, c[0], c[1], c[2], c[3]);
+  for (int i = 0; i < 4; i++) put(x[i]);
+  put(f29_lin4(x[0], c[0], x[1], c[1], x[2], c[2], x[3], c[3]));
+  printf("\n");
+}
+// sum of n products, the first writing the rows; must equal the zeroed-rows sum word for word
+void prod(int n, const q2* a, const q2* b, int contract) {
+  W29 w, z;
+  w29_set(w, a[0], b[0]);
+  for (int t = 1; t < n; t++) w29_mac(w, a[t], b[t]);
+  w29_init(z);
+  for (int t = 0; t < n; t++) w29_mac(z, a[t], b[t]);
+  const q2 r = w29_reduce(w), rz = w29_reduce(z);
+  int same = 1;
+  for (int i = 0; i < 9; i++) same &= r.c0.l[i] == rz.c0.l[i] && r.c1.l[i] == rz.c1.l[i];
+  printf("prod %d %d %d", contract, n, same);
+  for (int t = 0; t < n; t++) {
+    put(a[t]);
+    put(b[t]);
+  }
+  put(r);
+  printf("\n");
+}
+// the fixed line's sum: two products, then row / R + f in the reduction
+void fline(const q2 a[2], const q2 b[2], const q2& f, int contract) {
+  W29 w, z;
+  w29_init(w);
+  w29_init(z);
+  for (int t = 0; t < 2; t++) {
+    w29_mac(w, a[t], b[t]);
+    w29_mac(z, a[t], b[t]);
+  }
+  const q2 g = w29_reduce_add(w, f), r = w29_reduce(z);
+  printf("fline %d", contract);
+  put(f);
+  put(r);
+  put(g);
+  printf("\n");
+}
+
+q2 rnd_q2() { return {rnd_bal(), rnd_bal()}; }
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const int n_rand = argc > 1 ? atoi(argv[1]) : 1500;
+  const int32_t top = TOP_HALF;
+  // ------------------------------------------------------------ lin2
+  const int32_t c2[][2] = {{9, -1}, {1, 9}, {3, -2}, {6, 2}, {1, 1}, {1, 0}, {2, 0}, {16, 16}, {16, -16},
+                           {-16, 16}, {-16, -16}, {1, -1}, {0, 0}};
+  for (const auto& c : c2)
+    for (uint32_t s = 0; s < 4; s++) {
+      const uint32_t sa = s & 1 ? 0xFF : 0, sb = s & 2 ? 0xFF : 0;
+      lin2(corner(B28, sa, sa ? -top : top), c[0], corner(B28, sb, sb ? -top : top), c[1], 1);
+      lin2(corner(1 << 29, sa, sa ? -top : top), c[0], corner(1 << 29, sb, sb ? -top : top), c[1], 1);
+      lin2(corner(B28, 0x55, sa ? -top : top), c[0], corner(B28, 0xAA, sb ? -top : top), c[1], 1);
+      lin2(half_p(sa != 0), c[0], half_p(sb != 0), c[1], 1);
+    }
+  for (int k = -2; k <= 2; k++)
+    for (int m = -2; m <= 2; m++) {  // multiples of p: the result is zero, limb for limb
+      lin2(mult_p(k), 7, mult_p(m), 3, 2);
+      lin2(mult_p(k), 16, mult_p(m), -16, 2);
+      lin2(mult_p(k), 1, mult_p(m), 0, 2);
+    }
+  {  // f29_breduce of f29_from_fp outputs: limbs in [0, 2^29), value up to 32 p
+    f29 a;
+    for (int i = 0; i < 8; i++) a.l[i] = F29_MASK;
+    a.l[8] = 32 * 3171407;
+    lin2(a, 1, a, 0, 1);
+    for (int i = 0; i < 8; i++) a.l[i] = 0;
+    lin2(a, 1, a, 0, 1);
+  }
+  for (int i = 0; i < n_rand; i++) {
+    const auto& c = c2[rnd() % 12];
+    const bool wild = (rnd() & 3) == 0;
+    lin2(rnd_bal(), wild ? rnd_in(-16, 16) : c[0], rnd_bal(), wild ? rnd_in(-16, 16) : c[1], 1);
+  }
+  // ------------------------------------------------------------ lin4
+  const int32_t c4[][4] = {{3, -30, 3, -2},  {3, -3, -30, -2}, {0, 54, -6, 2},   {0, 6, 54, 2},     {0, 6, 0, 2},
+                           {0, 0, 6, 2},     {64, 64, 64, 64}, {-64, 64, -64, 64}, {64, -64, -64, 64}, {-64, -64, -64, -64},
+                           {1, 1, 1, 0},     {0, 0, 0, 0}};
+  for (const auto& c : c4)
+    for (uint32_t s = 0; s < 16; s++) {
+      f29 x[4], y[4], h[4];
+      for (int i = 0; i < 4; i++) {
+        const bool neg = (s >> i) & 1;
+        x[i] = corner(B28, neg ? 0xFF : 0, neg ? -top : top);
+        y[i] = corner(B28, neg ? 0x5A : 0xA5, neg ? -top : top);
+        h[i] = half_p(neg);
+      }
+      lin4(x, c, 1);
+      lin4(y, c, 1);
+      lin4(h, c, 1);
+    }
+  for (int k = -2; k <= 2; k++) {
+    const f29 x[4] = {mult_p(k), mult_p(-k), mult_p(2), mult_p(1)};
+    const int32_t c[4] = {64, 13, -5, 64};
+    lin4(x, c, 2);
+  }
+  for (int i = 0; i < n_rand; i++) {
+    f29 x[4] = {rnd_bal(), rnd_bal(), rnd_bal(), rnd_bal()};
+    int32_t c[4];
+    const bool wild = (rnd() & 3) == 0;
+    for (int j = 0; j < 4; j++) c[j] = wild ? rnd_in(-64, 64) : c4[rnd() % 10][j];
+    lin4(x, c, 1);
+  }
+  // ------------------------------------------------------------ products
+  {
+    // every limb product of the re (signs 0) or im (signs 1) column sums positive: the
+    // column bound itself, 6 terms of 2^28 x 2^28 and 3 terms of 2^29 x 2^28 (the
+    // squaring's doubled operand); limb 8 at 2^28 overstates any value (contract 0:
+    // congruence and limb bounds only)
+    for (int im = 0; im < 2; im++)
+      for (int neg = 0; neg < 2; neg++) {
+        q2 a[6], b[6];
+        const int32_t v = neg ? -B28 : B28;
+        for (int t = 0; t < 6; t++) {
+          a[t] = {corner(B28, 0, B28), corner(B28, 0, B28)};
+          b[t] = im ? q2{corner(B28, neg ? 0xFF : 0, v), corner(B28, neg ? 0xFF : 0, v)}
+                    : q2{corner(B28, neg ? 0xFF : 0, v), corner(B28, neg ? 0 : 0xFF, -v)};
+        }
+        prod(6, a, b, 0);
+        for (int t = 0; t < 3; t++) a[t] = {corner(1 << 29, 0, B28), corner(1 << 29, 0, B28)};
+        prod(3, a, b, 0);
+        prod(1, a, b, 0);
+      }
+    // the same signs with limb 8 of a value of p/2: in contract
+    for (int neg = 0; neg < 2; neg++) {
+      q2 a[6], b[6];
+      for (int t = 0; t < 6; t++) {
+        a[t] = {corner(B28, 0, top), corner(B28, 0, top)};
+        b[t] = {corner(B28, neg ? 0xFF : 0, neg ? -top : top), corner(B28, neg ? 0 : 0xFF, neg ? top : -top)};
+      }
+      for (int n = 1; n <= 6; n++) prod(n, a, b, 1);
+    }
+  }
+  for (int i = 0; i < n_rand / 3; i++) {
+    q2 a[6], b[6];
+    const int n = 1 + (int)(rnd() % 6);
+    for (int t = 0; t < n; t++) {
+      a[t] = rnd_q2();
+      b[t] = rnd_q2();
+    }
+    prod(n, a, b, 1);
+  }
+  // ------------------------------------------------------------ fixed line sum
+  {
+    const f29 hp = half_p(false), hn = half_p(true);
+    for (uint32_t s = 0; s < 8; s++) {
+      const bool neg = s & 1;
+      q2 a[2], b[2];
+      for (int t = 0; t < 2; t++) {
+        a[t] = {corner(B28, 0, top), corner(B28, 0, top)};
+        // the wrapped operand xi f: carry-swept, limb 8 up to 30 p
+        b[t] = {corner(B28, neg ? 0xFF : 0, (neg ? -30 : 30) * 3171407), corner(B28, neg ? 0 : 0xFF, (neg ? 30 : -30) * 3171407)};
+      }
+      // f: limbs at the balanced and at the 2^29 bound, limb 8 of 3 p (the prover chain's bound)
+      const int32_t lim = (s & 2) ? (1 << 29) : B28;
+      const int32_t t8 = ((s & 4) ? 3 : 1) * 3171407;
+      q2 f = {corner(lim, neg ? 0xFF : 0, neg ? -t8 : t8), corner(lim, neg ? 0 : 0xFF, neg ? t8 : -t8)};
+      fline(a, b, f, 0);
+      f = {neg ? hn : hp, neg ? hp : hn};
+      fline(a, b, f, 0);
+    }
+  }
+  for (int i = 0; i < n_rand / 3; i++) {
+    const q2 a[2] = {rnd_q2(), rnd_q2()}, b[2] = {rnd_q2(), rnd_q2()};
+    fline(a, b, rnd_q2(), 1);
+  }
+  return 0;
+}
