@@ -22,7 +22,7 @@ from . import _abi
 from ._abi import (FTZ_ERR_MALFORMED, FTZ_ERR_MEMBERSHIP, FTZ_ERR_OPENING, FTZ_ERR_PANIC,  # noqa: F401
                    FTZ_ERR_PARSE, FTZ_ERR_RANGE, FTZ_ERR_WF, FTZ_OK, KERNEL_NAMES, MESSAGES)
 
-__all__ = ["Context", "Batch", "Msm", "Prover", "ZKError", "Idemix", "OwnerVerifier", "TransferVerifier", "IssueVerifier", "transfer_zkproof_validate",
+__all__ = ["Context", "Batch", "Msm", "Prover", "ZKError", "Idemix", "OwnerVerifier", "Ecdsa", "EcdsaVerifier", "TransferVerifier", "IssueVerifier", "transfer_zkproof_validate",
            "FTZ_OK", "MESSAGES"]
 
 
@@ -689,6 +689,87 @@ class OwnerVerifier:
     def verify(self, message, sigma):
         """Verifier.Verify(message, sigma): raises ZKError on a reject."""
         code = self.ix.verify_owner_signatures([(self.owner, bytes(message), bytes(sigma))])[0]
+        if code != FTZ_OK:
+            raise ZKError(code)
+
+
+class Ecdsa:
+    """Batched x509 ECDSA P-256 signature verification: the auditor's and the
+    issuers' signatures of a request and fabtoken owners
+    (x509.MSPIdentityDeserializer -> identity/msp/x509/ecdsa.go:70-101
+    edsaVerifier.Verify) with SHA-256 and the curve arithmetic on the GPU.
+    Identities that sign often are registered once (add_identity) and named by
+    key index; others are passed as bytes and decoded per call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        _check(self._lib.ftz_ecdsa_create(ctx._h, ctypes.byref(h)), self._lib)
+        self._h = h
+
+    def add_identity(self, identity):
+        """register proto(msp.SerializedIdentity) -> key index (the same bytes give the same index)"""
+        key = ctypes.c_int32()
+        identity = bytes(identity)
+        _check(self._lib.ftz_ecdsa_add_identity(self._h, identity, len(identity), ctypes.byref(key)), self._lib)
+        return key.value
+
+    def verify_signatures(self, items):
+        """items: (identity bytes or registered key index, msg, sig) -> FTZ codes (0 = the signature verifies)"""
+        items = list(items)
+        arr, keep = _abi.pack_ecdsa_sigs(items)
+        return self.verify_signatures_packed(arr, len(items))
+
+    def verify_signatures_packed(self, arr, n):
+        """pre-packed ftz_ecdsa_sig array (bench: the binding's packing stays out of the timed call)"""
+        codes = (ctypes.c_int32 * max(n, 1))()
+        _check(self._lib.ftz_verify_ecdsa_signatures(self._h, n, arr, codes), self._lib)
+        return list(codes[:n])
+
+    def public_key(self, identity):
+        """the identity's P-256 key as X || Y (64 bytes); raises ZKError(FTZ_ERR_IDENTITY / _UNSUPPORTED)"""
+        return x509_public_key(identity, self._lib)
+
+    def verifier(self, identity):
+        """DeserializeVerifier(identity): identity bytes or a registered key index"""
+        return EcdsaVerifier(self, identity)
+
+    def close(self):
+        if self._h:
+            self._lib.ftz_ecdsa_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def x509_public_key(identity, lib=None):
+    """Host only: the P-256 public key X || Y of proto(msp.SerializedIdentity)."""
+    lib = lib or _abi.load()
+    identity = bytes(identity)
+    xy = ctypes.create_string_buffer(64)
+    code = lib.ftz_x509_public_key(identity, len(identity), xy)
+    if code < 0:
+        _check(code, lib)
+    if code != FTZ_OK:
+        raise ZKError(code)
+    return xy.raw
+
+
+class EcdsaVerifier:
+    """driver.Verifier of an x509 identity (identity/msp/x509/ecdsa.go:66-101)."""
+
+    def __init__(self, ec, identity):
+        self.ec = ec
+        self.identity = identity if isinstance(identity, int) else bytes(identity)
+
+    def verify(self, message, sigma):
+        """Verifier.Verify(message, sigma): raises ZKError on a reject."""
+        code = self.ec.verify_signatures([(self.identity, bytes(message), bytes(sigma))])[0]
         if code != FTZ_OK:
             raise ZKError(code)
 

@@ -87,6 +87,39 @@ def pack_owner_sigs(items):
     return arr, keep
 
 
+FTZ_ERR_IDENTITY = 13
+MESSAGES[FTZ_ERR_IDENTITY] = "failed parsing received public key: the identity is not an ECDSA public key"
+
+
+class EcdsaSig(ctypes.Structure):
+    _fields_ = [("identity", ctypes.c_void_p), ("identity_len", ctypes.c_size_t), ("key", ctypes.c_int32),
+                ("msg", ctypes.c_void_p), ("msg_len", ctypes.c_size_t), ("sig", ctypes.c_void_p),
+                ("sig_len", ctypes.c_size_t)]
+
+
+def pack_ecdsa_sigs(items):
+    """items: (identity bytes or registered key index, msg, sig); identical
+    identity / msg objects share one buffer.  Returns (ftz_ecdsa_sig array, keepalive)."""
+    items = list(items)
+    arr = (EcdsaSig * max(len(items), 1))()
+    keep = []
+    bufs = {}
+
+    def buf(b):
+        k = id(b)
+        if k not in bufs:
+            bufs[k] = ctypes.create_string_buffer(bytes(b), max(len(b), 1))
+            keep.append((b, bufs[k]))
+        return ctypes.cast(bufs[k], ctypes.c_void_p)
+
+    for i, (who, m, s_) in enumerate(items):
+        if isinstance(who, int):
+            arr[i] = EcdsaSig(None, 0, who, buf(m), len(m), buf(s_), len(s_))
+        else:
+            arr[i] = EcdsaSig(buf(who), len(who), -1, buf(m), len(m), buf(s_), len(s_))
+    return arr, keep
+
+
 FTZ_FEXP_EXACT = 0
 FTZ_FEXP_FUENTES = 1
 FEXP = {"exact": FTZ_FEXP_EXACT, "fuentes": FTZ_FEXP_FUENTES}
@@ -285,6 +318,7 @@ SYMBOLS = ["ftz_options_default", "ftz_ctx_create", "ftz_ctx_create_ex", "ftz_ct
            "ftz_batch_destroy", "ftz_batch_challenges", "ftz_msm_g1", "ftz_msm_load", "ftz_msm_load_gen", "ftz_msm_run", "ftz_msm_set_scalars", "ftz_msm_run_scalars", "ftz_host_alloc", "ftz_host_free", "ftz_msm_info", "ftz_msm_destroy", "ftz_g1_sum",
            "ftz_token_request_decode", "ftz_verify_token_requests", "ftz_verify_token_requests_batched", "ftz_ctx_request_stats",
            "ftz_idemix_create", "ftz_verify_owner_signatures", "ftz_idemix_set_strict_nym", "ftz_idemix_destroy", "ftz_audit_owners",
+           "ftz_ecdsa_create", "ftz_ecdsa_add_identity", "ftz_verify_ecdsa_signatures", "ftz_x509_public_key", "ftz_ecdsa_destroy",
            "ftz_prove_transfers", "ftz_prove_issues", "ftz_ctx_prover_stats", "ftz_prover_load_transfers", "ftz_prover_load_issues",
            "ftz_prover_run", "ftz_prover_submit", "ftz_prover_wait", "ftz_prover_bytes", "ftz_prover_proofs", "ftz_prover_stats", "ftz_prover_destroy"]
 
@@ -375,6 +409,12 @@ def load():
     lib.ftz_idemix_set_strict_nym.argtypes = [vp, ctypes.c_int]
     lib.ftz_idemix_destroy.argtypes = [vp]
     lib.ftz_idemix_destroy.restype = None
+    lib.ftz_ecdsa_create.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.ftz_ecdsa_add_identity.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(i32)]
+    lib.ftz_verify_ecdsa_signatures.argtypes = [vp, sz, ctypes.POINTER(EcdsaSig), ctypes.POINTER(i32)]
+    lib.ftz_x509_public_key.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p]
+    lib.ftz_ecdsa_destroy.argtypes = [vp]
+    lib.ftz_ecdsa_destroy.restype = None
     lib.ftz_token_request_decode.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(sz), ctypes.POINTER(Bytes), sz]
     # the callback as a plain function pointer: a ctypes GET_STATE(S)_FN or a native one
     lib.ftz_verify_token_requests.argtypes = [vp, sz, ctypes.POINTER(Bytes), vp, vp,

@@ -425,6 +425,50 @@ typedef struct {
 } ftz_owner_audit;
 int ftz_audit_owners(ftz_idemix* ix, size_t n, const ftz_owner_audit* items, int32_t* codes);
 
+/* ---- x509 ECDSA P-256 signatures: the auditor's signature of a request
+ * (crypto/validator/validator.go:134-145), each issue action's issuer
+ * signature (validator.go:170-176) and fabtoken owners.  Replaces
+ * x509.MSPIdentityDeserializer.DeserializeVerifier (nogh/deserializer.go:56-57
+ * -> identity/msp/x509/ecdsa.go:130-147: proto msp.SerializedIdentity, one PEM
+ * block "PUBLIC KEY" or "CERTIFICATE") and edsaVerifier.Verify
+ * (ecdsa.go:70-101: asn1 signature, SHA-256, the low-S rule, ecdsa.Verify) on
+ * P-256 keys.  Identities that repeat across a block (the auditor, the issuers
+ * of the public parameters) are registered once with ftz_ecdsa_add_identity --
+ * at most 64 per handle, 510 KiB of device table each -- and named by index;
+ * an identity seen once is passed with key = -1 and decoded per call.  Only
+ * what is certain is decided here: FTZ_ERR_UNSUPPORTED means "verify this one
+ * in Go" (another curve, an RSA key, another PEM block type, a PEM block not
+ * in the canonical form, a certificate that departs from the expected DER
+ * walk).  A certificate's own signature, validity and chain are not checked,
+ * as in the reference; Go's x509.ParseCertificate is stricter than the walk to
+ * the key done here, so register only identities the Go deserializer has
+ * accepted (for the auditor and issuers: when the public parameters load).
+ * Not wired into ftz_verify_token_requests. */
+#define FTZ_ERR_IDENTITY 13 /* the identity does not deserialize to an ECDSA public key */
+typedef struct ftz_ecdsa ftz_ecdsa;
+typedef struct {
+  const uint8_t* identity; /* proto(msp.SerializedIdentity); read when key < 0           */
+  size_t identity_len;
+  int32_t key;             /* >= 0: a registered key; -1: decode `identity`               */
+  const uint8_t* msg;      /* the signed message (hashed on the device)                   */
+  size_t msg_len;
+  const uint8_t* sig;      /* DER ECDSA signature                                         */
+  size_t sig_len;
+} ftz_ecdsa_sig;
+int ftz_ecdsa_create(ftz_ctx* ctx, ftz_ecdsa** out);
+/* Decode the identity and build its table: *key = its index (the same identity
+ * bytes give the same index again).  FTZ_E_INVALID (reason in ftz_last_error)
+ * for an undecodable or unsupported identity and beyond 64 keys. */
+int ftz_ecdsa_add_identity(ftz_ecdsa* e, const uint8_t* id, size_t id_len, int32_t* key);
+/* codes[i] = FTZ_OK, FTZ_ERR_IDENTITY, FTZ_ERR_UNSUPPORTED or FTZ_ERR_SIGNATURE;
+ * an out-of-range key is FTZ_E_INVALID for the call; thread-safe */
+int ftz_verify_ecdsa_signatures(ftz_ecdsa* e, size_t n, const ftz_ecdsa_sig* s, int32_t* codes);
+/* Host only: the identity's P-256 public key as X || Y (32 bytes big-endian
+ * each).  Returns the per-item code (FTZ_OK, FTZ_ERR_IDENTITY,
+ * FTZ_ERR_UNSUPPORTED; the reason in ftz_last_error) or FTZ_E_INVALID. */
+int ftz_x509_public_key(const uint8_t* id, size_t id_len, uint8_t xy[64]);
+void ftz_ecdsa_destroy(ftz_ecdsa* e);
+
 /* ---- standalone BN254 G1 multi-scalar multiplication (BASELINE configs[2]):
  * out = sum_i k_i P_i as 64-byte gnark RawBytes.  Points: n x 64-byte
  * uncompressed RawBytes (must be canonical and on the curve); scalars: n x 32
