@@ -111,7 +111,24 @@ struct G1Job {
   uint32_t out;             // g1out index
   uint32_t bytes;           // arena offset for RawBytes (NONE: skip)
   uint32_t b64;             // arena offset for the 88 base64 chars of RawBytes (NONE: skip)
+  // sh_count != 0: the variable part is the sum of the variable partials of
+  // jobs [sh_first, sh_first + sh_count) of the same job array (earlier jobs,
+  // same vscal and vneg, each one unit-weight point: k sum P_i = sum k P_i), so
+  // the split path runs no chain of its own; vstart / vcount / vscal still
+  // describe the point for the one-lane path (job_g1).  0: own chain.
+  uint32_t sh_first, sh_count;
 };
+// Most siblings a job shares (wider sums keep their own chain).  The sibling
+// sum runs in the job's k_g1_combine lane: sh_count - 1 Jacobian additions of
+// 16 products against the 1,950 of a chain.  A combine wave costs what its
+// slowest lane costs, so 16 (sh_count - 1) products are paid by the whole wave
+// while a dropped chain saves 1,950 / 64 = 30 a wave: uniform batches (9 of a
+// wave's 64 lanes share, 274 saved) gain up to 18 siblings, and a lone wide
+// side among narrow ones loses 16 (sh_count - 1) - 30, which the cap holds to
+// 82 products a wave (4 % of one chain).
+static constexpr uint32_t G1_SHARE_MAX = 8;
+// does the split path run a GLV chain for the job's variable part?
+FTS_HD bool g1_own_chain(const G1Job& j) { return j.vscal != NONE && j.sh_count == 0; }
 
 struct G2Job {
   uint32_t fscal[3];
@@ -849,6 +866,7 @@ FTS_HD void job_g1_part(const G1Job* jobs, uint32_t n, uint32_t i, const VTerm* 
                         const uint32_t (*scal)[8], const G1Dev* tab, G1JDev* part, G1Dev* vtab) {
   uint32_t f = i / n, jb = i - f * n;
   const G1Job& j = jobs[jb];
+  if (f == 3 && j.sh_count) return;  // the siblings' partials (job_g1_sum_parts)
   g1j acc = jac_inf<fp>();
   if (f < 3) {
     if (f < j.nfix) acc = g1_fixed_acc(acc, tab, j.fbase[f], scal[j.fscal[f]]);
@@ -873,7 +891,15 @@ FTS_HD void job_g1_part(const G1Job* jobs, uint32_t n, uint32_t i, const VTerm* 
 }
 
 FTS_HD g1j job_g1_sum_parts(const G1Job& j, uint32_t jb, uint32_t n, const G1JDev* part) {
-  g1j acc = g1j_load(part[3 * (size_t)n + jb]);
+  // only the parts the work lists of k_g1_part hold are written (g1_part_lists)
+  g1j acc = jac_inf<fp>();
+  if (j.sh_count) {
+    // complete additions: equal siblings double, opposite ones cancel
+    acc = g1j_load(part[3 * (size_t)n + j.sh_first]);
+    for (uint32_t s = 1; s < j.sh_count; s++) acc = jac_add(acc, g1j_load(part[3 * (size_t)n + j.sh_first + s]));
+  } else if (j.vscal != NONE) {
+    acc = g1j_load(part[3 * (size_t)n + jb]);
+  }
   for (uint32_t f = 0; f < 3; f++)
     if (f < j.nfix) acc = jac_add(acc, g1j_load(part[(size_t)f * n + jb]));
   return acc;

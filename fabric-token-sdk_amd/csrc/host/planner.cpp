@@ -52,6 +52,10 @@ void Plan::clear() {
   out.clear();
   out_off.clear();
   item_off.clear();
+  g1fl.clear();
+  g1vl.clear();
+  g1pfl.clear();
+  g1pvl.clear();
   dev_pools = false;
   arena_len = out_len = 0;
   wire.clear();
@@ -368,6 +372,24 @@ class Builder {
     (feeds_pairing ? pl.g1p : pl.g1).push_back(j);
     return j.out;
   }
+  // The job just emitted (the last of `jobs`) takes its variable part from the
+  // partials of the `count` jobs before it when those are exactly its terms:
+  // each sibling one unit-weight point, added, under the job's scalar and sign
+  // (k sum P_i = sum k P_i).  Sides wider than G1_SHARE_MAX keep their chain.
+  void share_var(std::vector<G1Job>& jobs, uint32_t count) {
+    if (count == 0 || count > G1_SHARE_MAX || jobs.size() < (size_t)count + 1) return;
+    G1Job& j = jobs.back();
+    const uint32_t first = (uint32_t)(jobs.size() - 1 - count);
+    if (j.vscal == NONE || j.vcount != count) return;
+    for (uint32_t s = 0; s < count; s++) {
+      const G1Job& q = jobs[first + s];
+      if (q.vscal != j.vscal || q.vneg != j.vneg || q.vcount != 1 || q.sh_count) return;
+      const VTerm &a = pl.vt[j.vstart + s], &b = pl.vt[q.vstart];
+      if (a.pt != b.pt || a.flags || b.flags || vterm_w(a) != 1 || vterm_w(b) != 1) return;
+    }
+    j.sh_first = first;
+    j.sh_count = count;
+  }
   // a verification transcript's HashToZr slot (debug_challenges plans only)
   uint32_t dbg_scal() { return pp.debug_challenges ? pl.n_scal++ : NONE; }
   static VTerm vterm(uint32_t pt, uint64_t w = 1) {
@@ -544,6 +566,7 @@ bool Builder::wf_side(uint32_t tok_pt, uint32_t n, const std::vector<Ref>& vals,
     all.push_back(vterm(tok_pt + i));
   }
   g1job({{G1B_PED0, s_tn}, {G1B_PED1, s_sum}, {G1B_PED2, s_bfsum}}, all, s_chal, wfout_bytes + 64 * n);
+  share_var(pl.g1, n);  // c sum T_i from the c T_i of the jobs above
   return true;
 }
 
@@ -1148,7 +1171,7 @@ size_t elem_size(int s) {
     case PS_DEC: return sizeof(DecodeJob);
     case PS_ZR: return sizeof(ZrJob);
     case PS_SC: case PS_SC1: case PS_SCPOST: return sizeof(ScalJob);
-    case PS_SCLIST: return sizeof(uint32_t);
+    case PS_SCLIST: case PS_G1FL: case PS_G1VL: case PS_G1PFL: case PS_G1PVL: return sizeof(uint32_t);
     case PS_VT: return sizeof(VTerm);
     case PS_G1: case PS_G1P: return sizeof(G1Job);
     case PS_G2: return sizeof(G2Job);
@@ -1192,7 +1215,7 @@ size_t piece_count(const Plan& p, int s) {
     case PS_CP2: return p.cp2.size();
     case PS_OUT: return p.dev_pools ? p.out_len : p.out.size();
   }
-  return 0;
+  return 0;  // the work lists exist in flat plans only (flat_layout counts them)
 }
 
 // Piece `b` (indices local to b) written at base `o` of the sections dst[s]
@@ -1253,6 +1276,7 @@ void relocate_into(const Plan& b, const PieceBase& o, bool p2_g1out, bool keep_c
       for (int k = 0; k < j.nfix; k++) j.fscal[k] += o_scal;
       j.vstart += o_vt;
       j.vscal = rel(j.vscal, o_scal);
+      if (j.sh_count) j.sh_first += (uint32_t)o.sec[sec];
       j.out += o_g1;
       j.bytes = rel(j.bytes, o_arena);
       j.b64 = rel(j.b64, o_arena);
@@ -1341,9 +1365,32 @@ void relocate_piece(const Plan& b, const PieceBase& o, const FlatPlan& fp, uint8
   uint8_t* dst[PS_COUNT];
   for (int s = 0; s < PS_COUNT; s++) dst[s] = blob + fp.off[s];
   relocate_into(b, o, fp.p2_g1out, false, dst);
+  for (int side = 0; side < 2; side++) {
+    const int sec = side ? PS_G1P : PS_G1, fl = side ? PS_G1PFL : PS_G1FL, vl = side ? PS_G1PVL : PS_G1VL;
+    const std::vector<G1Job>& jobs = side ? b.g1p : b.g1;
+    g1_part_lists(jobs.data(), jobs.size(), o.sec[sec], fp.cnt[sec], reinterpret_cast<uint32_t*>(dst[fl]) + o.sec[fl],
+                  reinterpret_cast<uint32_t*>(dst[vl]) + o.sec[vl]);
+  }
 }
 
 }  // namespace
+
+void g1_list_counts(const std::vector<G1Job>& jobs, size_t& nf, size_t& nv) {
+  nf = nv = 0;
+  for (const G1Job& j : jobs) {
+    nf += j.nfix;
+    nv += g1_own_chain(j);
+  }
+}
+
+// per piece, term by term (f = 0, 1, 2) as the 4 n grid ran them
+void g1_part_lists(const G1Job* jobs, size_t cnt, size_t base, size_t n, uint32_t* fixed, uint32_t* var) {
+  for (uint32_t f = 0; f < 3; f++)
+    for (size_t k = 0; k < cnt; k++)
+      if (f < jobs[k].nfix) *fixed++ = (uint32_t)(f * n + base + k);
+  for (size_t k = 0; k < cnt; k++)
+    if (g1_own_chain(jobs[k])) *var++ = (uint32_t)(3 * n + base + k);
+}
 
 std::string flat_layout(const PlanWork& w, bool p2_g1out, FlatPlan& fp) {
   fp.p2_g1out = p2_g1out;
@@ -1363,6 +1410,13 @@ std::string flat_layout(const PlanWork& w, bool p2_g1out, FlatPlan& fp) {
       b.sec[s] = cur[s];
       cur[s] += piece_count(p, s);
     }
+    size_t nf, nv;
+    g1_list_counts(p.g1, nf, nv);
+    cur[PS_G1FL] += nf;
+    cur[PS_G1VL] += nv;
+    g1_list_counts(p.g1p, nf, nv);
+    cur[PS_G1PFL] += nf;
+    cur[PS_G1PVL] += nv;
     b.pts = (uint32_t)pts;
     b.scal = (uint32_t)scal;
     b.g1out = (uint32_t)g1;
@@ -1379,6 +1433,8 @@ std::string flat_layout(const PlanWork& w, bool p2_g1out, FlatPlan& fp) {
   for (int s = 0; s < PS_COUNT; s++)
     if (cur[s] >= IDX_LIMIT) return "batch too large for 32-bit job indices (split it into smaller batches)";
   if (pts >= IDX_LIMIT || scal >= IDX_LIMIT || g1 >= IDX_LIMIT || g2 >= IDX_LIMIT)
+    return "batch too large for 32-bit job indices (split it into smaller batches)";
+  if (cur[PS_G1] >= IDX_LIMIT / 2 || cur[PS_G1P] >= IDX_LIMIT / 2)  // part indices f n + jb, f <= 3
     return "batch too large for 32-bit job indices (split it into smaller batches)";
   fp.n_pts = (uint32_t)pts;
   fp.n_scal = (uint32_t)scal;
@@ -1514,6 +1570,10 @@ void plan_unflatten(const FlatPlan& fp, const uint8_t* blob, Plan& out) {
   take(out.cp, PS_CP);
   take(out.cp2, PS_CP2);
   take(out.out, PS_OUT);
+  take(out.g1fl, PS_G1FL);
+  take(out.g1vl, PS_G1VL);
+  take(out.g1pfl, PS_G1PFL);
+  take(out.g1pvl, PS_G1PVL);
   out.out_off = fp.out_off;
   out.item_off = fp.item_off;
   out.p2_g1out = fp.p2_g1out;

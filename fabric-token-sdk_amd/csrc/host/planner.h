@@ -112,6 +112,8 @@ struct Plan {
   std::vector<uint8_t> out;       // outer proof JSON templates, concatenated
   std::vector<uint32_t> out_off;  // per proof: start in `out` (plus a final end)
   std::vector<uint32_t> item_off; // openings: arena offset of the 128-byte result (recomputed | decoded)
+  // flattened plans only (plan_unflatten): the work lists of g1 / g1p (g1_part_lists)
+  std::vector<uint32_t> g1fl, g1vl, g1pfl, g1pvl;
   bool p2_g1out = false;          // PairJob.p2 indexes g1out (prover) instead of pts
   // device-initialised pools (prover shape templates): the arena / out bytes are
   // not held here -- cp / cp2 write them on the device -- only their lengths
@@ -181,7 +183,9 @@ class WorkPool {
 // (from pinned memory) and the device pointers are blob + offset.
 enum PlanSec : int {
   PS_WIRE, PS_ARENA, PS_DEC, PS_ZR, PS_SC, PS_SCLIST, PS_VT, PS_G1, PS_G1P, PS_G2, PS_PR, PS_SEG, PS_HPRE,
-  PS_HMAIN, PS_CK, PS_TX, PS_RND, PS_SC1, PS_SCPOST, PS_EMIT, PS_B64, PS_CP, PS_CP2, PS_OUT, PS_COUNT
+  PS_HMAIN, PS_CK, PS_TX, PS_RND, PS_SC1, PS_SCPOST, PS_EMIT, PS_B64, PS_CP, PS_CP2, PS_OUT,
+  // work lists of k_g1_part (g1_part_lists), derived from the job arrays when the plan is flattened
+  PS_G1FL, PS_G1VL, PS_G1PFL, PS_G1PVL, PS_COUNT
 };
 static constexpr size_t WIRE_TAIL = 64;  // zero bytes after the wire pool (decode jobs may read past a short element)
 
@@ -208,6 +212,15 @@ struct FlatPlan {
   template <class T>
   T* ptr(uint8_t* blob, PlanSec s) const { return reinterpret_cast<T*>(blob + off[s]); }
 };
+
+// Work lists of k_g1_part over a job array of n jobs, as part indices
+// i = f n + jb (job_g1_part): `fixed` holds every real fixed-base term (f <
+// nfix) and `var` (i = 3 n + jb) every job that runs its own GLV chain
+// (g1_own_chain), so that the kernel's waves are uniform in kind and full.
+// Counts of a piece's jobs, and the entries of jobs [0, cnt) placed at job
+// index `base` of the array (written to fixed[0 .. nf), var[0 .. nv)).
+void g1_list_counts(const std::vector<G1Job>& jobs, size_t& nf, size_t& nv);
+void g1_part_lists(const G1Job* jobs, size_t cnt, size_t base, size_t n, uint32_t* fixed, uint32_t* var);
 
 // Reusable planning state of one batch slot: per-thread pieces keep their
 // buffers between batches, so steady-state planning does not allocate.

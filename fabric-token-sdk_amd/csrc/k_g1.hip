@@ -19,12 +19,23 @@ using namespace fts;
   if (i >= (n)) return;
 
 // Uniform parts of the G1 jobs (fixed-base slots and GLV variable parts), one
-// lane per part: lanes [f n, (f+1) n) all run the same code path.
-__global__ void __launch_bounds__(128) k_g1_part(const G1Job* jobs, uint32_t n, const VTerm* vt, const G1Dev* pts,
-                                                 const uint32_t (*scal)[8], const G1Dev* tab, G1JDev* part,
-                                                 G1Dev* vtab) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 4 * n) return;
+// lane per part of the plan's two dense work lists (host/planner.h
+// g1_part_lists): the fixed-base terms from lane 0, the variable chains from
+// the next multiple of 64, so every wave runs one code path and only the last
+// wave of each list is partly filled.  Grid: g1_part_lanes(nfl, nvl) lanes.
+__global__ void __launch_bounds__(128) k_g1_part(const G1Job* jobs, uint32_t n, const uint32_t* flist, uint32_t nfl,
+                                                 const uint32_t* vlist, uint32_t nvl, const VTerm* vt,
+                                                 const G1Dev* pts, const uint32_t (*scal)[8], const G1Dev* tab,
+                                                 G1JDev* part, G1Dev* vtab) {
+  const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x, vbase = (nfl + 63) & ~63u;
+  uint32_t i;
+  if (lane < vbase) {
+    if (lane >= nfl) return;
+    i = flist[lane];
+  } else {
+    if (lane - vbase >= nvl) return;
+    i = vlist[lane - vbase];
+  }
 #if FTS_G1PART_PRIO
   __builtin_amdgcn_s_setprio(FTS_G1PART_PRIO);
 #endif

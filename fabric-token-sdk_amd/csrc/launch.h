@@ -60,8 +60,11 @@ __global__ void k_verdict(const TxChecks* tx, uint32_t n, const Check* ck, const
                           const uint8_t* hash_ok, int32_t* codes, uint32_t* bitmap);
 __global__ void k_pp_decode(const uint8_t* raw, const uint32_t* g1off, uint32_t n1, const uint32_t* g2off,
                             uint32_t n2, G1Dev* g1, G2Dev* g2, uint8_t* g1bytes, uint8_t* g2bytes, uint8_t* ok);
-__global__ void k_g1_part(const G1Job* jobs, uint32_t n, const VTerm* vt, const G1Dev* pts,
-                          const uint32_t (*scal)[8], const G1Dev* tab, G1JDev* part, G1Dev* vtab);
+__global__ void k_g1_part(const G1Job* jobs, uint32_t n, const uint32_t* flist, uint32_t nfl, const uint32_t* vlist,
+                          uint32_t nvl, const VTerm* vt, const G1Dev* pts, const uint32_t (*scal)[8], const G1Dev* tab,
+                          G1JDev* part, G1Dev* vtab);
+// lanes of a k_g1_part launch: the fixed list padded to a whole wave, then the variable list
+static inline uint32_t g1_part_lanes(uint32_t nfl, uint32_t nvl) { return ((nfl + 63) & ~63u) + nvl; }
 __global__ void k_g1_combine(const G1Job* jobs, uint32_t n, const G1JDev* part, G1Dev* g1out, uint8_t* arena,
                              G1Dev* pnorm);
 __global__ void k_tab_g1(const G1Dev* bases, uint32_t n, G1Dev* tab);

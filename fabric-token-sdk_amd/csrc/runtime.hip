@@ -565,6 +565,7 @@ struct SlotPtrs {
   const uint32_t* sclist;
   const VTerm* vt;
   const G1Job *g1, *g1p;
+  const uint32_t *g1fl, *g1vl, *g1pfl, *g1pvl;  // k_g1_part work lists
   const G2Job* g2;
   const PairJob* pr;
   const Seg* seg;
@@ -590,6 +591,7 @@ struct SlotPtrs {
   int32_t* codes;
   uint32_t* bitmap;
   uint32_t n_dec, n_zr, n_sc, n_sc1, n_sp, n_rnd, n_em, n_b64, n_g1, n_g1p, n_g2, n_pr, n_hp, n_hm, n_tx, n_cp, n_cp2;
+  uint32_t n_g1fl, n_g1vl, n_g1pfl, n_g1pvl;
 };
 
 static SlotPtrs slot_ptrs(ftz_batch* b) {
@@ -609,6 +611,10 @@ static SlotPtrs slot_ptrs(ftz_batch* b) {
   p.vt = f.ptr<VTerm>(d, PS_VT);
   p.g1 = f.ptr<G1Job>(d, PS_G1);
   p.g1p = f.ptr<G1Job>(d, PS_G1P);
+  p.g1fl = f.ptr<uint32_t>(d, PS_G1FL);
+  p.g1vl = f.ptr<uint32_t>(d, PS_G1VL);
+  p.g1pfl = f.ptr<uint32_t>(d, PS_G1PFL);
+  p.g1pvl = f.ptr<uint32_t>(d, PS_G1PVL);
   p.g2 = f.ptr<G2Job>(d, PS_G2);
   p.pr = f.ptr<PairJob>(d, PS_PR);
   p.seg = f.ptr<Seg>(d, PS_SEG);
@@ -651,6 +657,10 @@ static SlotPtrs slot_ptrs(ftz_batch* b) {
   p.n_b64 = (uint32_t)f.cnt[PS_B64];
   p.n_g1 = (uint32_t)f.cnt[PS_G1];
   p.n_g1p = (uint32_t)f.cnt[PS_G1P];
+  p.n_g1fl = (uint32_t)f.cnt[PS_G1FL];
+  p.n_g1vl = (uint32_t)f.cnt[PS_G1VL];
+  p.n_g1pfl = (uint32_t)f.cnt[PS_G1PFL];
+  p.n_g1pvl = (uint32_t)f.cnt[PS_G1PVL];
   p.n_g2 = (uint32_t)f.cnt[PS_G2];
   p.n_pr = (uint32_t)f.cnt[PS_PR];
   p.n_hp = (uint32_t)f.cnt[PS_HPRE];
@@ -670,6 +680,20 @@ static hipError_t upload_plan(ftz_batch* b, hipStream_t s) {
   if (e == hipSuccess && f.dev_pools)
     e = hipMemcpyAsync(b->d_blob.p + f.off[PS_ARENA], b->h_blob.p + f.off[PS_ARENA], C_SIZE, hipMemcpyHostToDevice, s);
   return e;
+}
+
+// The G1 jobs of the pairing chain (pairing) or the side jobs: their parts
+// from the plan's work lists, then the sums to affine.
+static void launch_g1(const SlotPtrs& p, bool pairing, const G1Dev* tab, hipStream_t s) {
+  const G1Job* jobs = pairing ? p.g1p : p.g1;
+  const uint32_t n = pairing ? p.n_g1p : p.n_g1;
+  const uint32_t nfl = pairing ? p.n_g1pfl : p.n_g1fl, nvl = pairing ? p.n_g1pvl : p.n_g1vl;
+  G1JDev* part = pairing ? p.part1p : p.part1;
+  if (const uint32_t lanes = g1_part_lanes(nfl, nvl))
+    k_g1_part<<<blocks_for(lanes, 128), 128, 0, s>>>(jobs, n, pairing ? p.g1pfl : p.g1fl, nfl,
+                                                     pairing ? p.g1pvl : p.g1vl, nvl, p.vt, p.pts, p.scal, tab, part,
+                                                     pairing ? p.vtab1p : p.vtab1);
+  k_g1_combine<<<blocks_for(n, 256), 256, 0, s>>>(jobs, n, part, p.g1out, p.arena, p.pnorm);
 }
 
 // t' and the pair-2 lines (R read from `pts`): one lane per job (default;
@@ -751,18 +775,14 @@ int slot_submit(ftz_batch* b, bool upload, bool fetch_codes) {
   // st[0]: pairing chain
   HC(hipEventRecord(e[16], s));
   if (p.n_g1p) {
-    k_g1_part<<<blocks_for(4 * p.n_g1p, 128), 128, 0, s>>>(p.g1p, p.n_g1p, p.vt, p.pts, p.scal, c->g1tab.p, p.part1p,
-                                                           p.vtab1p);
-    k_g1_combine<<<blocks_for(p.n_g1p, 256), 256, 0, s>>>(p.g1p, p.n_g1p, p.part1p, p.g1out, p.arena, p.pnorm);
+    launch_g1(p, true, c->g1tab.p, s);
   }
   HC(hipEventRecord(e[5], s));
   // st[1]: pairing-independent G1 jobs, started with the jobs the chain waits for
   HC(hipStreamWaitEvent(s2, e[4], 0));
   HC(hipEventRecord(e[11], s2));
   if (p.n_g1) {
-    k_g1_part<<<blocks_for(4 * p.n_g1, 128), 128, 0, s2>>>(p.g1, p.n_g1, p.vt, p.pts, p.scal, c->g1tab.p, p.part1,
-                                                           p.vtab1);
-    k_g1_combine<<<blocks_for(p.n_g1, 256), 256, 0, s2>>>(p.g1, p.n_g1, p.part1, p.g1out, p.arena, p.pnorm);
+    launch_g1(p, false, c->g1tab.p, s2);
   }
   HC(hipEventRecord(e[12], s2));
   HC(hipStreamWaitEvent(s, e[15], 0));
@@ -989,17 +1009,13 @@ int prover_submit(ftz_batch* b, bool upload, bool fetch) {
   HC(hipStreamWaitEvent(s2, e[4], 0));
   HC(hipEventRecord(e[11], s2));
   if (p.n_g1) {
-    k_g1_part<<<blocks_for(4 * p.n_g1, 128), 128, 0, s2>>>(p.g1, p.n_g1, p.vt, p.pts, p.scal, prover_g1tab(c), p.part1,
-                                                           p.vtab1);
-    k_g1_combine<<<blocks_for(p.n_g1, 256), 256, 0, s2>>>(p.g1, p.n_g1, p.part1, p.g1out, p.arena, p.pnorm);
+    launch_g1(p, false, prover_g1tab(c), s2);
   }
   HC(hipEventRecord(e[12], s2));
   // st[0]: R' = rr R and rsbf P (the pairing inputs)
   HC(hipEventRecord(e[16], s));
   if (p.n_g1p) {
-    k_g1_part<<<blocks_for(4 * p.n_g1p, 128), 128, 0, s>>>(p.g1p, p.n_g1p, p.vt, p.pts, p.scal, prover_g1tab(c), p.part1p,
-                                                           p.vtab1p);
-    k_g1_combine<<<blocks_for(p.n_g1p, 256), 256, 0, s>>>(p.g1p, p.n_g1p, p.part1p, p.g1out, p.arena, p.pnorm);
+    launch_g1(p, true, prover_g1tab(c), s);
   }
   HC(hipEventRecord(e[5], s));
   // st[2]: t = rv PK1 + rh PK2 and its lines evaluated at R' (pair 2 reads g1out);
