@@ -26,6 +26,7 @@ OBJ = os.path.join(HERE, "build", "obj")
 LIB = os.path.join(HERE, "zkatdlog", "_lib", "libftsamd.so")
 MADPEAK = os.path.join(HERE, "zkatdlog", "_lib", "libftsmadpeak.so")
 FPCHECK = os.path.join(HERE, "zkatdlog", "_lib", "libftsfpcheck.so")
+DEVCHECK = os.path.join(HERE, "zkatdlog", "_lib", "libftsdevcheck.so")  # tests: device primitive conformance
 CALLERS = os.path.join(HERE, "zkatdlog", "_lib", "libftscallers.so")  # bench: closed-loop n=1 callers
 ARCH = os.environ.get("FTS_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -118,9 +119,11 @@ def build(jobs=8, force=False, verbose=True):
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n%s\n%s%s" % (" ".join(cmd), r.stdout, r.stderr))
+    tool_time = max(hdr_time, newest(glob.glob(os.path.join(CSRC, "tools", "*.h"))))
     for src, out in ((os.path.join(CSRC, "tools", "madpeak.hip"), MADPEAK),
-                     (os.path.join(CSRC, "tools", "fpcheck.hip"), FPCHECK)):
-        if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), hdr_time):
+                     (os.path.join(CSRC, "tools", "fpcheck.hip"), FPCHECK),
+                     (os.path.join(CSRC, "tools", "devcheck.hip"), DEVCHECK)):
+        if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), tool_time):
             r = subprocess.run([HIPCC] + FLAGS + ["-shared", src, "-o", out], capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError("tool build failed:\n" + r.stderr)
