@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ecdsa_k.h"
+#include "ecsign_k.h"
 #include "host/x509id.h"
 #include "rt_internal.h"
 
@@ -25,6 +26,15 @@ struct EcdsaSlot {
   bool busy = false;
 };
 
+// One pipeline slot of the signer: pinned staging, device blob / nonces / digests / partials / r || s, its stream.
+struct EcsignSlot {
+  PinnedMem h_blob, h_out;
+  DevMem d_blob, d_out, d_k, d_e, d_part;
+  hipStream_t st = nullptr;
+  size_t a = 0, m = 0;  // the slot's signatures: call-relative [a, a + m)
+  bool busy = false;
+};
+
 struct ftz_ecdsa {
   ftz_ctx* ctx = nullptr;
   DBuf<P256Aff> tabs;                  // table 0: G; table 1 + k: registered key k (all allocated at creation)
@@ -33,7 +43,18 @@ struct ftz_ecdsa {
   std::mutex mu;                       // one call on the device at a time
   WorkPool* pool = nullptr;            // host decoding threads
   EcdsaSlot slot[2];                   // chunk k+1 is decoded and laid out while chunk k runs
+  // signing (ftz_ecdsa_add_signer / ftz_sign_ecdsa): the private scalars live on the device only
+  std::vector<P256Aff> gtab;           // host copy of table 0 (public keys of new signers)
+  DBuf<uint32_t> skeys;                // ECSIGN_MAX_SIGNERS x 8 limbs, allocated with the first signer
+  int32_t n_signers = 0;
+  EcsignSlot sslot[2];                 // streams created by the first signing call
   ~ftz_ecdsa() {
+    for (EcsignSlot& q : sslot)
+      if (q.st) {
+        (void)hipStreamSynchronize(q.st);
+        (void)hipStreamDestroy(q.st);
+      }
+    if (skeys.p) (void)hipMemset(skeys.p, 0, skeys.n * sizeof(uint32_t));
     for (EcdsaSlot& q : slot)
       if (q.st) {
         (void)hipStreamSynchronize(q.st);
@@ -187,6 +208,7 @@ extern "C" int ftz_ecdsa_create(ftz_ctx* ctx, ftz_ecdsa** out) {
     delete e;
     return set_err(FTZ_E_DEVICE, std::string("ECDSA table upload failed: ") + hipGetErrorString(he));
   }
+  e->gtab = std::move(g);
   *out = e;
   return FTZ_SUCCESS;
 }
@@ -258,6 +280,184 @@ extern "C" int ftz_verify_ecdsa_signatures(ftz_ecdsa* e, size_t n, const ftz_ecd
   }
   for (EcdsaSlot& q : e->slot) {
     int r2 = ecdsa_collect(q, codes);
+    if (rc == FTZ_SUCCESS) rc = r2;
+  }
+  return rc;
+}
+
+// ------------------------------------------------------------------ signing
+// edsaSigner.Sign (identity/msp/x509/ecdsa.go:50-64) in batches: SHA-256, the
+// RFC 6979 nonce, k G, r, s and ToLowS on the GPU (k_ecsign_pre / _part /
+// _fin, dev/ecsign.h), DER on the host pool.  The nonces never leave the device.
+namespace {
+constexpr size_t ECSIGN_ITEM_BYTES = sizeof(EcsignJob) + 32 + 16;  // job, entropy, message alignment
+static_assert(ECSIGN_MAX_SIGNERS == FTZ_ECDSA_MAX_SIGNERS, "the device array holds what the header promises");
+
+// wait for a slot's pass and write its DER signatures
+int ecsign_collect(ftz_ecdsa* e, EcsignSlot& q, uint8_t* sigs, uint32_t* sig_lens, int32_t* codes) {
+  if (!q.busy) return FTZ_SUCCESS;
+  q.busy = false;
+  HC(hipStreamSynchronize(q.st));
+  const uint8_t* rs = q.h_out.p;
+  const uint8_t* ok = q.h_out.p + q.m * 64;
+  e->pool->run((q.m + 63) / 64, [&](size_t p) {
+    for (size_t k = p * 64; k < q.m && k < (p + 1) * 64; k++) {
+      uint8_t* out = sigs + (q.a + k) * FTZ_ECDSA_SIG_MAX;
+      memset(out, 0, FTZ_ECDSA_SIG_MAX);
+      if (!ok[k]) {
+        sig_lens[q.a + k] = 0;
+        codes[q.a + k] = FTZ_ERR_SIGNATURE;
+        continue;
+      }
+      sig_lens[q.a + k] = (uint32_t)ftsh::encode_ecdsa_signature(rs + k * 64, rs + k * 64 + 32, out);
+      codes[q.a + k] = FTZ_OK;
+    }
+  });
+  return FTZ_SUCCESS;
+}
+
+// lay out it[a..b) and queue its device pass
+int ecsign_chunk(ftz_ecdsa* e, EcsignSlot& q, const ftz_ecdsa_sign_item* it, size_t a, size_t b) {
+  const size_t m = b - a;
+  // blob: jobs | every distinct message (same pointer and length) once, 16-aligned | 32 entropy bytes per hedged job
+  std::vector<EcsignJob> jobs(m);
+  std::vector<uint8_t> copies(m, 0);
+  std::unordered_map<const uint8_t*, std::pair<uint32_t, uint32_t>> seen;  // pointer -> (offset, length)
+  size_t off = (m * sizeof(EcsignJob) + 15) & ~(size_t)15;
+  for (size_t k = 0; k < m; k++) {
+    const ftz_ecdsa_sign_item& s = it[a + k];
+    jobs[k].msg_len = (uint32_t)s.msg_len;
+    jobs[k].signer = s.signer;
+    jobs[k].entropy = 0;
+    if (s.entropy) {
+      jobs[k].entropy = (uint32_t)off;
+      off += 32;
+    }
+    auto f = s.msg_len ? seen.find(s.msg) : seen.end();
+    if (f != seen.end() && f->second.second == s.msg_len) {
+      jobs[k].msg = f->second.first;
+      continue;
+    }
+    jobs[k].msg = (uint32_t)off;
+    copies[k] = 1;
+    if (s.msg_len) seen[s.msg] = {(uint32_t)off, (uint32_t)s.msg_len};
+    off += (s.msg_len + 15) & ~(size_t)15;
+  }
+  const size_t total = off + 64;  // slack: the SHA-256 block loads never leave the buffer
+  HC(q.h_blob.reserve(total));
+  HC(q.d_blob.reserve(total));
+  HC(q.h_out.reserve(m * 65));
+  HC(q.d_out.reserve(m * 65));
+  HC(q.d_k.reserve(m * 32));
+  HC(q.d_e.reserve(m * 32));
+  HC(q.d_part.reserve(ECSIGN_PARTS * m * sizeof(P256Jac)));
+  uint8_t* blob = q.h_blob.p;
+  memcpy(blob, jobs.data(), m * sizeof(EcsignJob));
+  e->pool->run((m + 63) / 64, [&](size_t p) {
+    for (size_t k = p * 64; k < m && k < (p + 1) * 64; k++) {
+      const ftz_ecdsa_sign_item& s = it[a + k];
+      if (s.entropy) memcpy(blob + jobs[k].entropy, s.entropy, 32);
+      if (copies[k] && s.msg_len) memcpy(blob + jobs[k].msg, s.msg, s.msg_len);
+    }
+  });
+  const EcsignJob* djobs = reinterpret_cast<const EcsignJob*>(q.d_blob.p);
+  const uint32_t(*keys)[8] = reinterpret_cast<const uint32_t(*)[8]>(e->skeys.p);
+  uint32_t(*dk)[8] = reinterpret_cast<uint32_t(*)[8]>(q.d_k.p);
+  uint32_t(*de)[8] = reinterpret_cast<uint32_t(*)[8]>(q.d_e.p);
+  P256Jac* part = reinterpret_cast<P256Jac*>(q.d_part.p);
+  uint8_t* d_rs = q.d_out.p;
+  uint8_t* d_ok = q.d_out.p + m * 64;
+  HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, off, hipMemcpyHostToDevice, q.st));
+  const uint32_t g1 = (uint32_t)((m + 63) / 64), g4 = (uint32_t)((ECSIGN_PARTS * m + 63) / 64);
+  k_ecsign_pre<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, q.d_blob.p, keys, dk, de);
+  k_ecsign_part<<<g4, 64, 0, q.st>>>((uint32_t)m, dk, e->tabs.p, part);
+  k_ecsign_fin<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, keys, part, dk, de, d_rs, d_ok);
+  HC(hipGetLastError());
+  HC(hipMemcpyAsync(q.h_out.p, q.d_out.p, m * 65, hipMemcpyDeviceToHost, q.st));
+  // nothing secret stays behind the pass: the nonces (k_ecsign_fin has zeroed its own), the digests
+  // and the partial sums of k G, from which the windows of k could be read back
+  HC(hipMemsetAsync(q.d_k.p, 0, m * 32, q.st));
+  HC(hipMemsetAsync(q.d_e.p, 0, m * 32, q.st));
+  HC(hipMemsetAsync(q.d_part.p, 0, ECSIGN_PARTS * m * sizeof(P256Jac), q.st));
+  q.a = a;
+  q.m = m;
+  q.busy = true;
+  return FTZ_SUCCESS;
+}
+}  // namespace
+
+extern "C" int ftz_ecdsa_add_signer(ftz_ecdsa* e, const uint8_t d[32], int32_t* signer, uint8_t public_xy[64]) {
+  if (!e || !d || !signer) return set_err(FTZ_E_INVALID, "null argument");
+  uint32_t dl[8];
+  be32_to_limbs(dl, d);
+  if (u256_is_zero(dl) || u256_geq(dl, P256_N)) {
+    explicit_bzero(dl, sizeof dl);
+    return set_err(FTZ_E_INVALID, "private scalar not in [1, n)");
+  }
+  std::lock_guard<std::mutex> lk(e->mu);
+  int rc = FTZ_SUCCESS;
+  hipError_t he = hipSuccess;
+  if (e->n_signers >= ECSIGN_MAX_SIGNERS) {
+    rc = set_err(FTZ_E_INVALID, "too many signers (at most " + std::to_string(ECSIGN_MAX_SIGNERS) + ")");
+  } else {
+    he = hipSetDevice(e->ctx->device);
+    if (he == hipSuccess && !e->skeys.p) {
+      he = e->skeys.alloc((size_t)ECSIGN_MAX_SIGNERS * 8);
+      if (he == hipSuccess) he = hipMemset(e->skeys.p, 0, e->skeys.n * sizeof(uint32_t));
+    }
+    if (he == hipSuccess && public_xy) {  // d G on the host; d < n is no multiple of n: never infinity
+      p256j q = p256_fixed_mul(e->gtab.data(), dl);
+      pf zi = pf_inv(q.z);
+      pf zi2 = pf_sqr(zi);
+      uint32_t t[8];
+      pf_to_int(t, q.x * zi2);
+      limbs_to_be32(public_xy, t);
+      pf_to_int(t, q.y * zi2 * zi);
+      limbs_to_be32(public_xy + 32, t);
+    }
+    // no pass is in flight (a signing call holds the mutex until it has collected its slots)
+    if (he == hipSuccess)
+      he = hipMemcpy(e->skeys.p + (size_t)e->n_signers * 8, dl, sizeof dl, hipMemcpyHostToDevice);
+    if (he == hipSuccess) *signer = e->n_signers++;
+  }
+  explicit_bzero(dl, sizeof dl);
+  if (he != hipSuccess) return set_err(FTZ_E_DEVICE, std::string("signer upload failed: ") + hipGetErrorString(he));
+  return rc;
+}
+
+extern "C" int ftz_sign_ecdsa(ftz_ecdsa* e, size_t n, const ftz_ecdsa_sign_item* it, uint8_t* sigs,
+                              uint32_t* sig_lens, int32_t* codes) {
+  if (!e || (n && (!it || !sigs || !sig_lens || !codes))) return set_err(FTZ_E_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  for (size_t i = 0; i < n; i++) {
+    if (!it[i].msg && it[i].msg_len) return set_err(FTZ_E_INVALID, "null buffer with non-zero length");
+    if (it[i].msg_len > ECDSA_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
+    if (it[i].signer < 0 || it[i].signer >= e->n_signers)
+      return set_err(FTZ_E_INVALID, "signer " + std::to_string(it[i].signer) + " is not a registered signer");
+  }
+  if (n == 0) return FTZ_SUCCESS;
+  HC(hipSetDevice(e->ctx->device));
+  for (EcsignSlot& q : e->sslot)
+    if (!q.st) HC(hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
+  // chunks of <= ECDSA_CHUNK_SIGS signatures and < ECDSA_CHUNK_BYTES of blob, alternating
+  // between the two slots: chunk k+1 is laid out while chunk k runs
+  size_t a = 0, c = 0;
+  int rc = FTZ_SUCCESS;
+  while (a < n && rc == FTZ_SUCCESS) {
+    size_t b = a, bytes = 0;
+    while (b < n && b - a < ECDSA_CHUNK_SIGS &&
+           (b == a || bytes + it[b].msg_len + ECSIGN_ITEM_BYTES < ECDSA_CHUNK_BYTES)) {
+      bytes += it[b].msg_len + ECSIGN_ITEM_BYTES;
+      b++;
+    }
+    EcsignSlot& q = e->sslot[c & 1];
+    rc = ecsign_collect(e, q, sigs, sig_lens, codes);
+    if (rc == FTZ_SUCCESS) rc = ecsign_chunk(e, q, it, a, b);
+    a = b;
+    c++;
+  }
+  for (EcsignSlot& q : e->sslot) {
+    int r2 = ecsign_collect(e, q, sigs, sig_lens, codes);
     if (rc == FTZ_SUCCESS) rc = r2;
   }
   return rc;

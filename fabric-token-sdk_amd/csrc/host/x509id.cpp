@@ -182,6 +182,23 @@ int decode_ecdsa_signature(const uint8_t* sig, size_t len, uint8_t r[32], uint8_
   return fts::ecdsa_rs_in_range(rl, sl8) ? FTZ_OK : FTZ_ERR_SIGNATURE;
 }
 
+size_t encode_ecdsa_signature(const uint8_t r[32], const uint8_t s[32], uint8_t out[72]) {
+  size_t n = 2;  // the SEQUENCE header: its content is at most 70 bytes, one length byte
+  for (const uint8_t* v : {r, s}) {
+    size_t lead = 0;
+    while (lead < 31 && v[lead] == 0) lead++;  // zero keeps one byte
+    const bool pad = (v[lead] & 0x80) != 0;
+    out[n++] = 0x02;
+    out[n++] = (uint8_t)(32 - lead + (pad ? 1 : 0));
+    if (pad) out[n++] = 0;
+    memcpy(out + n, v + lead, 32 - lead);
+    n += 32 - lead;
+  }
+  out[0] = 0x30;
+  out[1] = (uint8_t)(n - 2);
+  return n;
+}
+
 int decode_x509_identity(const uint8_t* id, size_t len, uint8_t xy[64], std::string* why) {
   std::vector<PbField> fs;
   std::string e = pb_scan(id, len, fs);

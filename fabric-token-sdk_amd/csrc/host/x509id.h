@@ -40,6 +40,12 @@ namespace ftsh {
 // FTZ_OK with r, s (32 bytes big-endian, in range), or FTZ_ERR_SIGNATURE
 int decode_ecdsa_signature(const uint8_t* sig, size_t len, uint8_t r[32], uint8_t s[32]);
 
+// The writer's side (edsaSigner.Sign, ecdsa.go:50-64, utils.MarshalECDSASignature):
+// SEQUENCE of two minimal INTEGERs -- leading zero bytes stripped, a 0x00 pad
+// when the top bit is set.  r, s: 32 bytes big-endian, any values; returns the
+// length written, at most 72 (71 for a low s).
+size_t encode_ecdsa_signature(const uint8_t r[32], const uint8_t s[32], uint8_t out[72]);
+
 // FTZ_OK with the affine point X || Y (32 bytes big-endian each, on P-256), or
 // FTZ_ERR_IDENTITY / FTZ_ERR_UNSUPPORTED with the reason in *why (optional)
 int decode_x509_identity(const uint8_t* id, size_t len, uint8_t xy[64], std::string* why = nullptr);

@@ -22,7 +22,7 @@ from . import _abi
 from ._abi import (FTZ_ERR_MALFORMED, FTZ_ERR_MEMBERSHIP, FTZ_ERR_OPENING, FTZ_ERR_PANIC,  # noqa: F401
                    FTZ_ERR_PARSE, FTZ_ERR_RANGE, FTZ_ERR_WF, FTZ_OK, KERNEL_NAMES, MESSAGES)
 
-__all__ = ["Context", "Batch", "Msm", "Prover", "ZKError", "Idemix", "OwnerVerifier", "Ecdsa", "EcdsaVerifier", "TransferVerifier", "IssueVerifier", "transfer_zkproof_validate",
+__all__ = ["Context", "Batch", "Msm", "Prover", "ZKError", "Idemix", "OwnerVerifier", "Ecdsa", "EcdsaVerifier", "EcdsaSigner", "TransferVerifier", "IssueVerifier", "transfer_zkproof_validate",
            "FTZ_OK", "MESSAGES"]
 
 
@@ -735,6 +735,41 @@ class Ecdsa:
         """DeserializeVerifier(identity): identity bytes or a registered key index"""
         return EcdsaVerifier(self, identity)
 
+    def add_signer(self, d):
+        """register a private scalar (32 bytes big-endian, 1 <= d < n; at most 8
+        per handle) -> (signer index, public key X || Y)"""
+        d = bytes(d)
+        if len(d) != 32:
+            raise ValueError("the private scalar is 32 bytes big-endian")
+        idx = ctypes.c_int32()
+        xy = ctypes.create_string_buffer(64)
+        _check(self._lib.ftz_ecdsa_add_signer(self._h, d, ctypes.byref(idx), xy), self._lib)
+        return idx.value, xy.raw
+
+    def sign(self, items):
+        """items: (signer index, msg[, 32 entropy bytes or None]) -> DER signatures
+        (edsaSigner.Sign with the RFC 6979 nonce; with entropy, hedged by it)"""
+        items = list(items)
+        arr, keep = _abi.pack_ecdsa_sign_items(items)
+        return self.sign_packed(arr, len(items))
+
+    def sign_packed(self, arr, n):
+        """pre-packed ftz_ecdsa_sign_item array (bench: the binding's packing stays out of the timed call)"""
+        sigs = ctypes.create_string_buffer(max(n, 1) * _abi.FTZ_ECDSA_SIG_MAX)
+        lens = (ctypes.c_uint32 * max(n, 1))()
+        codes = (ctypes.c_int32 * max(n, 1))()
+        _check(self._lib.ftz_sign_ecdsa(self._h, n, arr, sigs, lens, codes), self._lib)
+        raw, out = sigs.raw, []
+        for i in range(n):
+            if codes[i] != FTZ_OK:
+                raise ZKError(codes[i])
+            out.append(raw[i * _abi.FTZ_ECDSA_SIG_MAX:i * _abi.FTZ_ECDSA_SIG_MAX + lens[i]])
+        return out
+
+    def signer(self, index):
+        """the driver.Signer of a registered private scalar"""
+        return EcdsaSigner(self, index)
+
     def close(self):
         if self._h:
             self._lib.ftz_ecdsa_destroy(self._h)
@@ -772,6 +807,18 @@ class EcdsaVerifier:
         code = self.ec.verify_signatures([(self.identity, bytes(message), bytes(sigma))])[0]
         if code != FTZ_OK:
             raise ZKError(code)
+
+
+class EcdsaSigner:
+    """driver.Signer of an x509 identity (identity/msp/x509/ecdsa.go:50-64)."""
+
+    def __init__(self, ec, index):
+        self.ec = ec
+        self.index = index
+
+    def sign(self, message, entropy=None):
+        """Signer.Sign(message): the DER signature"""
+        return self.ec.sign([(self.index, bytes(message), entropy)])[0]
 
 
 class SignatureError(Exception):

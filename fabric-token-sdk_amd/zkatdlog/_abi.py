@@ -120,6 +120,39 @@ def pack_ecdsa_sigs(items):
     return arr, keep
 
 
+FTZ_ECDSA_MAX_SIGNERS = 8
+FTZ_ECDSA_SIG_MAX = 72
+
+
+class EcdsaSignItem(ctypes.Structure):
+    _fields_ = [("msg", ctypes.c_void_p), ("msg_len", ctypes.c_size_t), ("signer", ctypes.c_int32),
+                ("entropy", ctypes.c_void_p)]
+
+
+def pack_ecdsa_sign_items(items):
+    """items: (signer index, msg[, 32 entropy bytes or None]); identical msg
+    objects share one buffer.  Returns (ftz_ecdsa_sign_item array, keepalive)."""
+    items = list(items)
+    arr = (EcdsaSignItem * max(len(items), 1))()
+    keep = []
+    bufs = {}
+
+    def buf(b):
+        k = id(b)
+        if k not in bufs:
+            bufs[k] = ctypes.create_string_buffer(bytes(b), max(len(b), 1))
+            keep.append((b, bufs[k]))
+        return ctypes.cast(bufs[k], ctypes.c_void_p)
+
+    for i, it in enumerate(items):
+        signer, m = it[0], it[1]
+        ent = it[2] if len(it) > 2 else None
+        if ent is not None and len(ent) != 32:
+            raise ValueError("entropy must be 32 bytes")
+        arr[i] = EcdsaSignItem(buf(m), len(m), signer, buf(ent) if ent is not None else None)
+    return arr, keep
+
+
 FTZ_FEXP_EXACT = 0
 FTZ_FEXP_FUENTES = 1
 FEXP = {"exact": FTZ_FEXP_EXACT, "fuentes": FTZ_FEXP_FUENTES}
@@ -319,6 +352,7 @@ SYMBOLS = ["ftz_options_default", "ftz_ctx_create", "ftz_ctx_create_ex", "ftz_ct
            "ftz_token_request_decode", "ftz_verify_token_requests", "ftz_verify_token_requests_batched", "ftz_ctx_request_stats",
            "ftz_idemix_create", "ftz_verify_owner_signatures", "ftz_idemix_set_strict_nym", "ftz_idemix_destroy", "ftz_audit_owners",
            "ftz_ecdsa_create", "ftz_ecdsa_add_identity", "ftz_verify_ecdsa_signatures", "ftz_x509_public_key", "ftz_ecdsa_destroy",
+           "ftz_ecdsa_add_signer", "ftz_sign_ecdsa",
            "ftz_prove_transfers", "ftz_prove_issues", "ftz_ctx_prover_stats", "ftz_prover_load_transfers", "ftz_prover_load_issues",
            "ftz_prover_run", "ftz_prover_submit", "ftz_prover_wait", "ftz_prover_bytes", "ftz_prover_proofs", "ftz_prover_stats", "ftz_prover_destroy"]
 
@@ -413,6 +447,9 @@ def load():
     lib.ftz_ecdsa_add_identity.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(i32)]
     lib.ftz_verify_ecdsa_signatures.argtypes = [vp, sz, ctypes.POINTER(EcdsaSig), ctypes.POINTER(i32)]
     lib.ftz_x509_public_key.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p]
+    lib.ftz_ecdsa_add_signer.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32), ctypes.c_char_p]
+    lib.ftz_sign_ecdsa.argtypes = [vp, sz, ctypes.POINTER(EcdsaSignItem), ctypes.c_char_p,
+                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(i32)]
     lib.ftz_ecdsa_destroy.argtypes = [vp]
     lib.ftz_ecdsa_destroy.restype = None
     lib.ftz_token_request_decode.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(sz), ctypes.POINTER(Bytes), sz]

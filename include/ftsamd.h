@@ -467,6 +467,42 @@ int ftz_verify_ecdsa_signatures(ftz_ecdsa* e, size_t n, const ftz_ecdsa_sig* s, 
  * each).  Returns the per-item code (FTZ_OK, FTZ_ERR_IDENTITY,
  * FTZ_ERR_UNSUPPORTED; the reason in ftz_last_error) or FTZ_E_INVALID. */
 int ftz_x509_public_key(const uint8_t* id, size_t id_len, uint8_t xy[64]);
+
+/* Signing on the same handle: the auditor's endorsement of a request
+ * (crypto/audit/auditor.go:118-135 Endorse -> Signer.Sign) and the issuers'
+ * signatures.  Replaces edsaSigner.Sign (identity/msp/x509/ecdsa.go:50-64):
+ * SHA-256, ecdsa.Sign, ToLowS, DER.  The nonce is RFC 6979's (HMAC-SHA-256 DRBG
+ * over the private key and the digest), computed on the device and never
+ * copied to the host.  With `entropy` = NULL a signature is a function of key
+ * and message; with 32 bytes of fresh randomness they enter as RFC 6979 3.6's
+ * additional data (a hedged nonce: a repeated seed still cannot repeat a nonce
+ * across two messages).  Go's ecdsa.Sign draws its nonce at random, so the
+ * bytes differ from the reference's; every signature passes edsaVerifier.Verify
+ * (minimal DER, 1 <= r < n, 1 <= s <= (n-1)/2).  Up to 8 private scalars per
+ * handle, kept in device memory (zeroed when the handle is destroyed); the
+ * library wipes its own host copy, the caller's buffer is the caller's to wipe.
+ * Table addresses depend on the nonce: for a process that owns its device.
+ * Not wired into ftz_verify_token_requests. */
+#define FTZ_ECDSA_MAX_SIGNERS 8
+#define FTZ_ECDSA_SIG_MAX 72 /* stride of the output; a low-S P-256 DER signature is <= 71 bytes */
+typedef struct {
+  const uint8_t* msg;     /* hashed on the device                                       */
+  size_t msg_len;
+  int32_t signer;         /* index from ftz_ecdsa_add_signer                            */
+  const uint8_t* entropy; /* NULL, or 32 bytes of fresh randomness mixed into the nonce */
+} ftz_ecdsa_sign_item;
+/* d: the private scalar, 32 bytes big-endian, 1 <= d < n (else FTZ_E_INVALID, as
+ * is a ninth signer).  public_xy (may be NULL) receives d G as X || Y, computed
+ * on the host, to build or check the signer's identity. */
+int ftz_ecdsa_add_signer(ftz_ecdsa* e, const uint8_t d[32], int32_t* signer, uint8_t public_xy[64]);
+/* sigs: n slots of FTZ_ECDSA_SIG_MAX bytes, sig_lens[i] of them written (the
+ * rest zero).  codes[i] = FTZ_OK; the one exception is FTZ_ERR_SIGNATURE
+ * (sig_lens[i] = 0) when r = 0 or s = 0, which has probability about 2^-256
+ * and which no known input reaches.  An out-of-range signer, a NULL message
+ * with a non-zero length or a message over 512 MiB is FTZ_E_INVALID for the
+ * call; thread-safe (one call at a time on the handle, verification included). */
+int ftz_sign_ecdsa(ftz_ecdsa* e, size_t n, const ftz_ecdsa_sign_item* it, uint8_t* sigs, uint32_t* sig_lens,
+                   int32_t* codes);
 void ftz_ecdsa_destroy(ftz_ecdsa* e);
 
 /* ---- standalone BN254 G1 multi-scalar multiplication (BASELINE configs[2]):
