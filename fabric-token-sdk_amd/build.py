@@ -6,7 +6,7 @@ source/header mtimes.  Output: zkatdlog/_lib/libftsamd.so (in-tree, so it
 travels to the GPU box with the repo snapshot).
 
     python fabric-token-sdk_amd/build.py [-j N] [--force]
-    python fabric-token-sdk_amd/build.py --variant NAME --defs "-DFTS_SX_KARA=0"
+    python fabric-token-sdk_amd/build.py --variant NAME --defs "-DFTS_G2_PART_WAVES=2"
 
 --variant builds an A/B library with extra defines into zkatdlog/_lib/ab/
 libftsamd_NAME.so (objects in build/obj_NAME); `bench.py --lib <path>`

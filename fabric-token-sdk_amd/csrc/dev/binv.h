@@ -14,9 +14,12 @@
 
 namespace fts {
 
-#ifndef FTS_BINV_PRIO
-#define FTS_BINV_PRIO 3  // wave priority of a tree launch: its lone Euclid shares a SIMD with other slots' waves
-#endif
+// wave priority while a lone inversion runs that other waves wait on (a tree
+// launch here, whose Euclid shares a SIMD with other slots' waves; wave 0 of
+// k_g1_combine's block inversion): profiles/r05/binv_prio_ab.txt,
+// combine_prio_ab.txt.  Raising the priority of k_g1_part or k_g2lines1 as
+// well measured noise (profiles/r05/kernel_prio_ab.txt).
+static constexpr int LONE_INV_PRIO = 3;
 
 // t = threadIdx.x (blockDim 256); get() is called only when active, put(v)
 // likewise; tree: 512 x 8 words of LDS (heap order: root 1, node i's children
@@ -24,7 +27,7 @@ namespace fts {
 template <class Get, class Put>
 __device__ __forceinline__ void binv_tree256(uint32_t (*tree)[8], uint32_t t, bool active, const Get& get,
                                              const Put& put) {
-  __builtin_amdgcn_s_setprio(FTS_BINV_PRIO);
+  __builtin_amdgcn_s_setprio(LONE_INV_PRIO);
   fp v = fe_one<ModP>();
   bool zero = false;
   if (active) {

@@ -129,11 +129,9 @@ FTS_HD uint32_t add8(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) {
   return c;
 }
 
-#ifndef FTS_ASM_CHAINS
-#define FTS_ASM_CHAINS 1  // device: modular add/sub and final subtractions as asm carry chains
-#endif
+// device: modular add/sub and final subtractions as asm carry chains
 #include "fp_asm.h"
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ASM_CHAINS
+#if defined(__HIP_DEVICE_COMPILE__)
 template <class M>
 __device__ __forceinline__ void addmod_asm(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]);
 template <>
@@ -168,7 +166,7 @@ __device__ __forceinline__ void condsub_asm<ModR>(uint32_t x[8]) {
 
 template <class M>
 FTS_HD Fe<M> operator+(const Fe<M>& a, const Fe<M>& b) {
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ASM_CHAINS
+#if defined(__HIP_DEVICE_COMPILE__)
   Fe<M> o;
   addmod_asm<M>(o.v, a.v, b.v);
   return o;
@@ -184,7 +182,7 @@ FTS_HD Fe<M> operator+(const Fe<M>& a, const Fe<M>& b) {
 
 template <class M>
 FTS_HD Fe<M> operator-(const Fe<M>& a, const Fe<M>& b) {
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ASM_CHAINS
+#if defined(__HIP_DEVICE_COMPILE__)
   Fe<M> o;
   submod_asm<M>(o.v, a.v, b.v);
   return o;
@@ -208,32 +206,17 @@ FTS_HD Fe<M> fe_dbl(const Fe<M>& a) {
   return a + a;
 }
 
-#include "fp_fips.h"
-#ifndef FTS_ONEASM
-#define FTS_ONEASM 1  // device: whole limb products as one asm statement (gen_oneasm.py)
-#endif
+// device: whole limb products as one asm statement (gen_oneasm.py)
 #include "fp_oneasm.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
+// Montgomery multiplication, FIPS (product scanning) with v_mad_u64_u32
 template <class M>
 __device__ __forceinline__ Fe<M> mont_mul_fips(const Fe<M>& a, const Fe<M>& b) {
-  Fe<M> x, y;
-#if FTS_ONEASM
+  Fe<M> x;
   mont_mul_oneasm<M>(x.v, a.v, b.v);
-#else
-  mont_mul_fips_limbs<M>(x.v, a.v, b.v);
-#endif
-#if FTS_ASM_CHAINS
   condsub_asm<M>(x.v);
-  (void)y;
   return x;
-#else
-  uint32_t pm[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) pm[j] = M::m[j];
-  uint32_t br = sub8(y.v, x.v, pm);
-  return br ? x : y;
-#endif
 }
 #endif
 
@@ -335,14 +318,10 @@ inline Fe<M> mont_mul_host64(const Fe<M>& a, const Fe<M>& b) {
 }
 #endif
 
-#ifndef FTS_MUL_IMPL
-#define FTS_MUL_IMPL 1  // 0: CIOS in C, 1: FIPS with inline v_mad_u64_u32 (device)
-#endif
-
 template <class M>
 FTS_HD Fe<M> operator*(const Fe<M>& a, const Fe<M>& b) {
   FTS_COUNT_MUL();
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_MUL_IMPL == 1
+#if defined(__HIP_DEVICE_COMPILE__)
   return mont_mul_fips(a, b);
 #elif !defined(__HIP_DEVICE_COMPILE__) && defined(FTS_HOST64)
   return mont_mul_host64(a, b);
@@ -543,15 +522,11 @@ FTS_HD fp fp_inv_eea(const fp& am) {
   fp r2 = fe_const<ModP>(P_R2);
   return (x * r2) * r2;
 }
-// the same inverse by Bernstein-Yang divsteps (dev/safegcd.h; checked against
-// fp_inv_eea on the device and the host); FTS_INV_EEA = 1 keeps the Euclid
-#ifndef FTS_INV_EEA
-#define FTS_INV_EEA 0
-#endif
-// divsteps on 30-bit limbs (default) or 62-bit limbs (FTS_INV_SG30 = 0)
-#ifndef FTS_INV_SG30
-#define FTS_INV_SG30 1
-#endif
+// the same inverse by Bernstein-Yang divsteps (dev/safegcd.h) on 30-bit or
+// 62-bit limbs.  fp_inv_var uses the 30-bit limbs; fp_inv_eea and
+// fp_inv_sg<62> remain as its independent references in devcheck and fpcheck
+// (tools/, tests/test_devcheck.py).  Divsteps against the Euclid:
+// profiles/r06/inv_safegcd.txt.
 template <int LIMBS>
 FTS_HD fp fp_inv_sg(const fp& am) {
   if (fe_is_zero(am)) return am;
@@ -564,15 +539,7 @@ FTS_HD fp fp_inv_sg(const fp& am) {
   fp r2 = fe_const<ModP>(P_R2);
   return (x * r2) * r2;
 }
-FTS_HD fp fp_inv_var(const fp& am) {
-#if FTS_INV_EEA
-  return fp_inv_eea(am);
-#elif FTS_INV_SG30
-  return fp_inv_sg<30>(am);
-#else
-  return fp_inv_sg<62>(am);
-#endif
-}
+FTS_HD fp fp_inv_var(const fp& am) { return fp_inv_sg<30>(am); }
 FTS_HD fr fr_inv(const fr& a) { return fe_pow<ModR>(a, R_MINUS_2); }
 
 // square root for p = 3 mod 4; returns false if a is not a square

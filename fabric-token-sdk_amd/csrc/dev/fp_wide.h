@@ -18,14 +18,17 @@
 
 namespace fts {
 
-#include "fp_wide_gen.h"
+// 6 p^2 and 2 p^2 (16 limbs): initial values of the lazily reduced real- and
+// imaginary-part accumulators
+static constexpr uint32_t P2X6[16] = {0xec307a26u, 0x63fa13ccu, 0x3b808607u, 0xe40c2b0eu, 0x9188c12bu, 0xbde093aau, 0xdc6d90b1u, 0x1a73b780u, 0x3ca8354eu, 0xe993de29u, 0x854c0424u, 0x20451fe6u, 0x13b4ecacu, 0x199e9ce8u, 0xc56c7daau, 0x36e29c52u};
+static constexpr uint32_t P2X2[16] = {0x4ebad362u, 0x76a8b144u, 0x13d58202u, 0x4c040e5au, 0xdb2d95b9u, 0x94a03138u, 0xf4248590u, 0x08d13d2au, 0x698d671au, 0x4ddbf4b8u, 0x2c6eac0cu, 0x60170aa2u, 0x0691a439u, 0xb334def8u, 0xec797f38u, 0x124b8970u};
+// 2p and p for the final conditional subtractions after REDC
+static constexpr uint32_t P_X2[8] = {0xb0f9fa8eu, 0x7841182du, 0xd0e3951au, 0x2f02d522u, 0x0302b0bbu, 0x70a08b6du, 0xc2634053u, 0x60c89ce5u};
 
 // r[16] = a[8] * b[8]
 FTS_HD void mul_wide(uint32_t r[16], const uint32_t a[8], const uint32_t b[8]) {
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ONEASM
+#if defined(__HIP_DEVICE_COMPILE__)
   mul_wide_oneasm(r, a, b);
-#elif defined(__HIP_DEVICE_COMPILE__)
-  mul_wide_asm(r, a, b);
 #else
   uint64_t acc = 0;
   uint32_t hi = 0;
@@ -50,10 +53,8 @@ FTS_HD void mul_wide(uint32_t r[16], const uint32_t a[8], const uint32_t b[8]) {
 FTS_HD fp redc_wide(const uint32_t t[16]) {
   FTS_COUNT_MAD(72);
   fp r;
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ONEASM
+#if defined(__HIP_DEVICE_COMPILE__)
   redc_wide_oneasm<ModP>(r.v, t);
-#elif defined(__HIP_DEVICE_COMPILE__)
-  redc_wide_asm(r.v, t);
 #else
   uint64_t acc = 0;
   uint32_t hi = 0;
@@ -83,7 +84,7 @@ FTS_HD fp redc_wide(const uint32_t t[16]) {
     hi = 0;
   }
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ASM_CHAINS
+#if defined(__HIP_DEVICE_COMPILE__)
   condsub2_p_asm(r.v);
   return r;
 #else
@@ -100,7 +101,7 @@ FTS_HD fp redc_wide(const uint32_t t[16]) {
 }
 
 FTS_HD void add16(uint32_t r[16], const uint32_t a[16]) {
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ASM_CHAINS
+#if defined(__HIP_DEVICE_COMPILE__)
   add16_asm(r, a);
   return;
 #endif
@@ -110,7 +111,7 @@ FTS_HD void add16(uint32_t r[16], const uint32_t a[16]) {
 }
 
 FTS_HD void sub16(uint32_t r[16], const uint32_t a[16]) {
-#if defined(__HIP_DEVICE_COMPILE__) && FTS_ASM_CHAINS
+#if defined(__HIP_DEVICE_COMPILE__)
   sub16_asm(r, a);
   return;
 #endif

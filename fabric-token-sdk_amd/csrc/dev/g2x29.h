@@ -1,10 +1,10 @@
 // Fixed-base G2 partial sums (k_g2_part) on the carry-free balanced form of the
 // sextet kernels (dev/fp29.h q2, dev/sx29.h w29_redc): the XYZZ mixed addition
 // (madd-2008-s, 8M + 2S; x2q_madd) over balanced Fp2 values instead of the
-// 32-bit Jacobian one of curve.h (a Jacobian q2 form, j2b_madd, is the
-// FTS_G2_PART_XYZZ=0 option: 8 % more VALU).  The rare doubling case (a running
-// sum equal to its next table point) redoes the lane in the 32-bit code, so
-// that its registers stay out of the loop (two waves per SIMD).
+// 32-bit Jacobian one of curve.h (a Jacobian q2 form, madd-2007-bl, took more
+// VALU instructions: profiles/r05/g2_part_xyzz2_ab.txt).  The rare doubling
+// case (a running sum equal to its next table point) redoes the lane in the
+// 32-bit code, so that its registers stay out of the loop (two waves per SIMD).
 //
 // One Fp2 product is q2_mulb: three 81-MAD limb-product rows (Karatsuba) folded
 // by columns into the two rows the balanced reductions need, reduced while they
@@ -23,10 +23,6 @@
 #include "sx29.h"
 
 namespace fts {
-
-#ifndef FTS_G2_PART_XYZZ
-#define FTS_G2_PART_XYZZ 1  // 1: the parts in XYZZ form (x2q_madd), 0: Jacobian (j2b_madd)
-#endif
 
 // Product scanning: column k of both result rows is formed, the reduction's
 // multiples m_i p_j (i + j = k) of the digits already chosen are added, and
@@ -80,33 +76,6 @@ FTS_HD q2 q2_mulb(const q2& a, const q2& b) {
       u += w29_p(a.c0.l[i], b.c0.l[j]);
       v += w29_p(a.c1.l[i], b.c1.l[j]);
       w += w29_p(sa.l[i], sb.l[j]);
-    }
-    scan2_step(s, k, (int64_t)(u - v), (int64_t)(w - (u + v)), r);
-  }
-  r.c0.l[8] = (int32_t)s.ar;
-  r.c1.l[8] = (int32_t)s.ai;
-  return r;
-}
-// a b + c d with one reduction (a, c limbs within 2^29; b, d balanced): the
-// four rows' columns stay below 36 x 2^57 + the reduction's terms < 2^63
-FTS_HD q2 q2_mul2b(const q2& a, const q2& b, const q2& c, const q2& d) {
-  FTS_COUNT_MAD(384);
-  FTS_SCHED_FENCE();
-  const f29 sa = f29_add(a.c0, a.c1), sb = f29_add(b.c0, b.c1);
-  const f29 sc = f29_add(c.c0, c.c1), sd = f29_add(d.c0, d.c1);
-  Scan2 s;
-  s.ar = s.ai = 0;
-  q2 r;
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    uint64_t u = 0, v = 0, w = 0;
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      const int j = k - i;
-      if (j < 0 || j > 8) continue;
-      u += w29_p(a.c0.l[i], b.c0.l[j]) + w29_p(c.c0.l[i], d.c0.l[j]);
-      v += w29_p(a.c1.l[i], b.c1.l[j]) + w29_p(c.c1.l[i], d.c1.l[j]);
-      w += w29_p(sa.l[i], sb.l[j]) + w29_p(sc.l[i], sd.l[j]);
     }
     scan2_step(s, k, (int64_t)(u - v), (int64_t)(w - (u + v)), r);
   }
@@ -178,7 +147,7 @@ FTS_HD x2q x2q_madd(const x2q& p, const q2& x2, const q2& y2, bool* dbl = nullpt
   const q2 R = q2_lin2b(q2_mulb(y2, p.zzz), 1, p.y, -1);
   if (q2_rzero(P)) {
     if (q2_rzero(R)) {
-      if (dbl) {  // as j2b_madd: the caller redoes the lane in the 32-bit code
+      if (dbl) {  // the caller redoes the lane in the 32-bit code
         *dbl = true;
         return p;
       }
@@ -212,75 +181,13 @@ FTS_HD g2j x2q_to_g2j(const x2q& p) {
   return {q2_to_fp2(X), q2_to_fp2(Y), q2_to_fp2(Z)};
 }
 
-// Jacobian form (X / Z^2, Y / Z^3): madd-2007-bl, 7M + 4S -- the same product
-// rows as the XYZZ addition with one coordinate fewer to keep live, which
-// brings the part kernel under the 256 registers of two waves per SIMD
-struct j2b {
-  q2 x, y, z;
-  bool inf;
-};
-// dbl-2009-l (a = 0), p not the identity
-FTS_HD j2b j2b_dbl(const j2b& p) {
-  const q2 A = q2_sqrb(p.x);
-  const q2 B = q2_sqrb(p.y);
-  const q2 C = q2_sqrb(B);
-  const q2 D = q2_lin3b(q2_sqrb(q2_lin2b(p.x, 1, B, 1)), 2, A, -2, C, -2);  // 2((X + B)^2 - A - C)
-  const q2 E = q2_lin2b(A, 3, A, 0);
-  const q2 X3 = q2_lin3b(q2_sqrb(E), 1, D, -2, D, 0);
-  const q2 Y3 = q2_lin2b(q2_mulb(E, q2_subr(D, X3)), 1, C, -8);
-  const q2 Z3 = q2_lin2b(q2_mulb(p.y, p.z), 2, p.y, 0);
-  return {X3, Y3, Z3, false};
-}
-// p + (x2, y2), (x2, y2) affine (balanced) and not the identity.  H = U2 - X
-// vanishes iff the x coordinates agree: the identity (r != 0), or p equals the
-// point -- then *dbl is set and p returned unchanged (the caller doubles; the
-// part kernel redoes the lane in the 32-bit code, so that the doubling's
-// registers do not count against the loop's)
-FTS_HD j2b j2b_madd(const j2b& p, const q2& x2, const q2& y2, bool* dbl = nullptr) {
-  if (p.inf) return {x2, y2, q2_one_b(), false};
-  const q2 Z1Z1 = q2_sqrb(p.z);
-  const q2 H = q2_lin2b(q2_mulb(x2, Z1Z1), 1, p.x, -1);
-  const q2 r = q2_lin2b(q2_mulb(y2, q2_mulb(p.z, Z1Z1)), 2, p.y, -2);  // 2 (S2 - Y)
-  if (q2_rzero(H)) {
-    if (q2_rzero(r)) {
-      if (dbl) {
-        *dbl = true;
-        return p;
-      }
-      return j2b_dbl({x2, y2, q2_one_b(), false});
-    }
-    j2b o = p;
-    o.inf = true;
-    return o;
-  }
-  const q2 HH = q2_sqrb(H);
-  const q2 Z3 = q2_lin3b(q2_sqrb(q2_lin2b(p.z, 1, H, 1)), 1, Z1Z1, -1, HH, -1);  // 2 Z H
-  const q2 I = q2_lin2b(HH, 4, HH, 0);
-  const q2 J = q2_mulb(H, I);
-  const q2 V = q2_mulb(p.x, I);
-  const q2 X3 = q2_lin3b(q2_sqrb(r), 1, J, -1, V, -2);
-  const q2 Y3 = q2_lin2b(q2_mulb(r, q2_subr(V, X3)), 1, q2_mulb(p.y, J), -2);
-  return {X3, Y3, Z3, false};
-}
-FTS_HD g2j j2b_to_g2j(const j2b& p) {
-  if (p.inf) return jac_inf<fp2>();
-  return {q2_to_fp2(p.x), q2_to_fp2(p.y), q2_to_fp2(p.z)};
-}
-
 // job_g2_part (dev/jobs.h) on this form: lane q of a job sums the table points
 // of the (base, window) positions q, q + 4, ...
 FTS_HD void job_g2_part_x29(const G2Job& g, int q, const uint32_t (*scal)[8], const G2Dev* tab, G2PartDev& out) {
-#if FTS_G2_PART_XYZZ
   x2q acc;
   acc.inf = true;
   acc.x = acc.y = acc.zz = acc.zzz = q2_zero();
   bool dbl = false;
-#else
-  j2b acc;
-  acc.inf = true;
-  acc.x = acc.y = acc.z = q2_zero();
-  bool dbl = false;
-#endif
 #pragma nounroll
   for (int p = q; p < 3 * G2TAB_WINDOWS; p += 4) {
     int f = p / G2TAB_WINDOWS, w = p % G2TAB_WINDOWS;
@@ -291,13 +198,8 @@ FTS_HD void job_g2_part_x29(const G2Job& g, int q, const uint32_t (*scal)[8], co
         const q2 x2 = q2_from_fp2(T.x);
         q2 y2 = q2_from_fp2(T.y);
         if (d < 0) y2 = q2_neg(y2);
-#if FTS_G2_PART_XYZZ
         acc = x2q_madd(acc, x2, y2, &dbl);
         if (dbl) break;
-#else
-        acc = j2b_madd(acc, x2, y2, &dbl);
-        if (dbl) break;
-#endif
       }
     }
   }
@@ -305,11 +207,7 @@ FTS_HD void job_g2_part_x29(const G2Job& g, int q, const uint32_t (*scal)[8], co
     job_g2_part(g, q, scal, tab, out);  // a running sum met its next table point
     return;
   }
-#if FTS_G2_PART_XYZZ
   g2part_store(out, x2q_to_g2j(acc));
-#else
-  g2part_store(out, j2b_to_g2j(acc));
-#endif
 }
 
 }  // namespace fts

@@ -481,15 +481,12 @@ FTS_HD g2j g2_fixed_acc(g2j acc, const G2Dev* tab, int base, const uint32_t s[8]
   return acc;
 }
 
-#ifndef FTS_G1_F29
-#define FTS_G1_F29 1  // G1 loops in the carry-free 29-bit form (dev/fp29.h); 0: fp.h throughout
-#endif
-
+// The G1 loops below run in the carry-free 29-bit form (dev/fp29.h); the same
+// loops on fp.h throughout were slower (no record kept).
+//
 // sum_w d_w 2^(C w) B over the signed C-bit digits of s (s < r < 2^254, so the
 // top window absorbs the last carry)
-FTS_HD g1j g1_fixed_acc_fp(g1j acc, const G1Dev* tab, int base, const uint32_t s[8]);
 FTS_HD g1j g1_fixed_acc(g1j acc, const G1Dev* tab, int base, const uint32_t s[8]) {
-#if FTS_G1_F29
   // runs of mixed additions: the XYZZ accumulator (fp29.h x29_madd)
   x29 a{};
   a.inf = is_zero(acc.z);
@@ -518,36 +515,13 @@ FTS_HD g1j g1_fixed_acc(g1j acc, const G1Dev* tab, int base, const uint32_t s[8]
     }
   }
   return j29_to(x29_to_j29(a));
-#else
-  return g1_fixed_acc_fp(acc, tab, base, s);
-#endif
-}
-FTS_HD g1j g1_fixed_acc_fp(g1j acc, const G1Dev* tab, int base, const uint32_t s[8]) {
-  uint32_t carry = 0;
-  const G1Dev* tb = tab + (size_t)base * G1TAB_WINDOWS * G1TAB_DIGITS;
-#pragma nounroll
-  for (int w = 0; w < G1TAB_WINDOWS; w++) {
-    uint32_t bit = (uint32_t)G1TAB_C * w, limb = bit >> 5, sh = bit & 31;
-    uint64_t lo = limb < 8 ? s[limb] : 0, hi = limb + 1 < 8 ? s[limb + 1] : 0;
-    uint32_t raw = (uint32_t)(((lo | (hi << 32)) >> sh) & ((1ull << G1TAB_C) - 1)) + carry;
-    int32_t d = (int32_t)raw;
-    carry = 0;
-    if (raw > (1u << (G1TAB_C - 1))) {
-      d = (int32_t)raw - (int32_t)(1u << G1TAB_C);
-      carry = 1;
-    }
-    if (d) {
-      g1a T = g1_load(tb[(size_t)w * G1TAB_DIGITS + (uint32_t)(d < 0 ? -d : d) - 1]);
-      if (d < 0) T.y = fe_neg(T.y);
-      acc = jac_add_aff(acc, T);
-    }
-  }
-  return acc;
 }
 
 // k P for affine P and a scalar k < r.  Joint double-and-add over the two
 // 128-bit GLV halves (Shamir): one mixed addition per bit with the operand
-// chosen among P', phi(P)', P' + phi(P)' -- uniform across the wave.
+// chosen among P', phi(P)', P' + phi(P)' -- uniform across the wave.  The jobs
+// use g1_mul_glv16 below (fewer additions; no record kept); this one remains as
+// the cross-reference of tests/native/emu.cpp (emu_g1_mul_glv).
 FTS_HD g1j g1_mul_glv(const g1a& p, const uint32_t k[8]) {
   g1j acc = jac_inf<fp>();
   if (p.inf) return acc;
@@ -684,7 +658,6 @@ FTS_HD g1j g1_mul_glv16_iso(const g1a& p, const fp& zin, const uint32_t k[8], G1
     g1dev_put(tb[e * st], X * s2, Y * (s2 * se));
   }
   const bool flip = n1 != n2;  // phi(e P1) = +-phi(e p): sign of the second half
-#if FTS_G1_F29
   const f29 beta29 = f29_reduce(f29_from_fp(fe_const<ModP>(GLV_BETA)));
   j29 a = {f29{}, f29{}, f29{}, true};
 #pragma nounroll
@@ -708,45 +681,9 @@ FTS_HD g1j g1_mul_glv16_iso(const g1a& p, const fp& zin, const uint32_t k[8], G1
     if (m2) a = na;
   }
   acc = j29_to(a);
-#else
-  const fp beta = fe_const<ModP>(GLV_BETA);
-#pragma nounroll
-  for (int i = 32; i >= 0; i--) {
-    int d1 = booth16(k1, i), d2 = booth16(k2, i);
-    int m1 = d1 < 0 ? -d1 : d1, m2 = d2 < 0 ? -d2 : d2;
-    fp x1, y1, x2, y2;
-    g1dev_get(tb[(size_t)(m1 ? m1 - 1 : 0) * st], x1, y1);
-    g1dev_get(tb[(size_t)(m2 ? m2 - 1 : 0) * st], x2, y2);
-    if (i != 32) {
-      acc = jac_dbl(acc);
-      acc = jac_dbl(acc);
-      acc = jac_dbl(acc);
-      acc = jac_dbl(acc);
-    }
-    g1a A;
-    A.x = x1;
-    A.y = (d1 < 0) ? fe_neg(y1) : y1;
-    A.inf = false;
-    g1j nacc = jac_add_aff(acc, A);
-    if (m1) acc = nacc;
-    A.x = x2 * beta;
-    A.y = ((d2 < 0) != flip) ? fe_neg(y2) : y2;
-    nacc = jac_add_aff(acc, A);
-    if (m2) acc = nacc;
-  }
-#endif
   acc.z = acc.z * (Zc * zin);  // back to E (the point at infinity keeps z = 0)
   return acc;
 }
-
-#ifndef FTS_G1_VAR_W
-#define FTS_G1_VAR_W 16  // 16: g1_mul_glv16 (signed 4-bit windows), 2: g1_mul_glv (joint binary)
-#endif
-#if FTS_G1_VAR_W == 16
-#define G1_MUL_VAR(P, K, TB, ST) g1_mul_glv16(P, K, TB, ST)
-#else
-#define G1_MUL_VAR(P, K, TB, ST) g1_mul_glv(P, K)
-#endif
 
 FTS_HD void g1_emit_bytes(const G1Job& j, const g1a& r, uint8_t* arena) {
   if (j.bytes != NONE) g1_to_bytes_g(arena + j.bytes, r);
@@ -873,7 +810,6 @@ FTS_HD void job_g1_part(const G1Job* jobs, uint32_t n, uint32_t i, const VTerm* 
   } else if (j.vscal != NONE) {
     g1j V = g1_var_point(j, vterms, pts);
     if (j.vneg) V = jac_neg(V);
-#if FTS_G1_VAR_W == 16
 #if defined(__HIP_DEVICE_COMPILE__)
     G1Dev* tb = vtab + jb;
     const size_t st = n;
@@ -883,9 +819,6 @@ FTS_HD void job_g1_part(const G1Job* jobs, uint32_t n, uint32_t i, const VTerm* 
     const size_t st = vtab ? n : 1;
 #endif
     if (!is_zero(V.z)) acc = g1_mul_glv16_iso(g1a{V.x, V.y, false}, V.z, scal[j.vscal], tb, st);
-#else
-    acc = g1_mul_glv(jac_to_aff(V), scal[j.vscal]);
-#endif
   }
   g1j_store(part[i], acc);
 }
@@ -1134,6 +1067,8 @@ FTS_HD g2j g2part_load(const G2PartDev& d) {
     }
   return a;
 }
+// the part in the 32-bit Jacobian form: job_g2_part_x29's doubling fallback
+// (dev/g2x29.h) and tests/native/sx_emu.cpp's cross-reference
 FTS_HD void job_g2_part(const G2Job& g, int q, const uint32_t (*scal)[8], const G2Dev* tab, G2PartDev& out) {
   g2j acc = jac_inf<fp2>();
 #pragma nounroll
@@ -1150,7 +1085,8 @@ FTS_HD void job_g2_part(const G2Job& g, int q, const uint32_t (*scal)[8], const 
   }
   g2part_store(out, acc);
 }
-// parts of job idx at part[q * njobs + idx]
+// parts of job idx at part[q * njobs + idx]; the 32-bit line chain
+// (tests/native/sx_emu.cpp's cross-reference of dev/g2lines29.h)
 FTS_HD void job_g2lines_parts(const G2Job& g, const PairJob& j, const G2PartDev* part, G2Dev* g2out,
                               const G1Dev* pts, EvLineDev* lines, uint32_t idx, uint32_t njobs) {
   g2j acc = g2part_load(part[idx]);

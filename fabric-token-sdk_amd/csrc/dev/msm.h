@@ -57,25 +57,11 @@ struct MsmPlan {
   uint64_t nv_magic;   // floor(2^32 / nv) + 1: the window of an entry t without a division
 };
 
-// k_msm_tree: parts per block (quad-cooperative additions: 128, one lane each: 256)
-#ifndef FTS_MSM_QUAD_TREE
-#define FTS_MSM_QUAD_TREE 1
-#endif
-static constexpr uint32_t MSM_TREE_CHUNK = FTS_MSM_QUAD_TREE ? 128u : 256u;
-// k_msm_segment: one quad per segment (64 per 256-lane block) or one lane each
-// (default: the quads measured slower, 2^16 segment stage 264 against 188 us,
-// 2^20 523 against 282, profiles/r06/msm_tail.txt)
-#ifndef FTS_MSM_QUAD_SEG
-#define FTS_MSM_QUAD_SEG 0
-#endif
-static constexpr uint32_t MSM_SEG_THREADS = FTS_MSM_QUAD_SEG ? 256u : 128u;
-static constexpr uint32_t MSM_SEG_PER_BLOCK = FTS_MSM_QUAD_SEG ? 64u : 128u;
-
-// the window combination (Horner) on the host from the read-back window sums
-// (msm_rt.hip msm_horner_host); 0: on one wave of the device (k_msm_horner)
-#ifndef FTS_MSM_HOST_HORNER
-#define FTS_MSM_HOST_HORNER 1
-#endif
+// k_msm_tree: parts per block (a quad of lanes per addition)
+static constexpr uint32_t MSM_TREE_CHUNK = 128;
+// k_msm_segment: one lane per segment
+static constexpr uint32_t MSM_SEG_THREADS = 128;
+static constexpr uint32_t MSM_SEG_PER_BLOCK = 128;
 
 // window bits for n (virtual) points: floor(log2 n / 2) + 7 clamped to [8, 20]
 // (measured on MI355X with GLV: 2^17 -> 15, 2^21 -> 17, 2^25 -> 19; the
@@ -334,11 +320,9 @@ FTS_HD g1j msm_job_slot(const MsmPlan& p, uint32_t j, const uint32_t* owner, con
   };
   uint32_t v = e[lo];
   G1Dev nxt = pts[point_of(v)];
-#if FTS_G1_F29
   // the additions in the carry-free XYZZ form (dev/fp29.h), one conversion per slot
   x29 a{};
   a.inf = true;
-#endif
   for (uint32_t q = lo; q < hi; q++) {
     // the next point's load is issued before this point's addition
     G1Dev cur = nxt;
@@ -348,20 +332,12 @@ FTS_HD g1j msm_job_slot(const MsmPlan& p, uint32_t j, const uint32_t* owner, con
       nxt = pts[point_of(v)];
     }
     g1a P = g1_load(cur);
-#if FTS_G1_F29
     if (!P.inf) {
       f29 Y = f29_from_fp(P.y);
       a = x29_madd(a, f29_from_fp(P.x), sign ? f29_neg(Y) : Y);
     }
-#else
-    if (sign) P = aff_neg(P);
-    acc = jac_add_aff(acc, P);
-#endif
   }
-#if FTS_G1_F29
-  acc = j29_to(x29_to_j29(a));
-#endif
-  return acc;
+  return j29_to(x29_to_j29(a));
 }
 
 // The reduction stages (segment, tree, Horner) are latency-bound chains of

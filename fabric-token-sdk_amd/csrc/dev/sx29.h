@@ -5,8 +5,9 @@
 // changes is the arithmetic under each lane's Fp2 sum  sum_t a_t b_t:
 //   - field elements are 9 signed 29-bit limbs (dev/fp29.h, Montgomery radix
 //     R = 2^261) kept BALANCED: every limb in [-2^28, 2^28], |value| <= p/2 + e;
-//   - a lane sums its Fp2 products schoolbook into two rows of 17 signed 64-bit
-//     columns (4 x 81 v_mad_i64_i32 per Fp2 product, no carries); one limb
+//   - a lane sums its Fp2 products into rows of 17 64-bit columns without
+//     carries (three Karatsuba rows, below, which stand for the two schoolbook
+//     rows re, im of 4 x 81 limb products per Fp2 product); one limb
 //     product is <= 2^56, so the 6 terms of an Fp12 product (12 field products
 //     per column, 9 limb products each: 108 x 2^56) plus the reduction's
 //     multiples of p (9 x 2^56) stay below 2^63;
@@ -26,7 +27,7 @@
 namespace fts {
 
 // ----------------------------------------------------------- accumulation
-// FTS_SX_KARA (default 1): the lane's Fp2 sum is kept as three Karatsuba rows
+// The lane's Fp2 sum is kept as three Karatsuba rows
 //   U = sum a0 b0,  V = sum a1 b1,  W = sum (a0 + a1)(b0 + b1)
 // (3 x 81 MADs per Fp2 product instead of the schoolbook 4 x 81), and the two
 // rows the reduction needs are formed once per sum: re = U - V, im = W - U - V.
@@ -36,12 +37,9 @@ namespace fts {
 // is unchanged, so every reduced value -- and every GT byte -- is bit-identical
 // to the schoolbook accumulation.  A complex square s^2 adds s0^2, s1^2 and
 // (s0 + s1)^2 to the rows as three 45-MAD squarings (doubled cross products).
-#ifndef FTS_SX_KARA
-#define FTS_SX_KARA 1
-#endif
+// Measured against the schoolbook rows in profiles/r05/karatsuba_ab.txt.
 // a limb product as an unsigned 64-bit term (rows that may wrap modulo 2^64)
 FTS_HD uint64_t w29_p(int32_t a, int32_t b) { return (uint64_t)((int64_t)a * (int64_t)b); }
-#if FTS_SX_KARA
 struct W29 {
   uint64_t u[17], v[17], w[17];
 };
@@ -88,34 +86,6 @@ FTS_HD void w29_sqr_acc(W29& w, const q2& s) {
   w29_row_sqr(w.v, s.c1);
   w29_row_sqr(w.w, f29_add(s.c0, s.c1));
 }
-#else
-struct W29 {
-  int64_t re[17], im[17];
-};
-FTS_HD void w29_init(W29& w) {
-#pragma unroll
-  for (int i = 0; i < 17; i++) w.re[i] = w.im[i] = 0;
-}
-// w += a b (a, b balanced); FIRST: w = a b, no zeroed rows (see above)
-template <bool FIRST>
-FTS_HD void w29_mac_t(W29& w, const q2& a, const q2& b) {
-  FTS_COUNT_MAD(192);  // the 32-bit equivalent (3 wide products), for opcounts
-  FTS_SCHED_FENCE();
-  f29 nb1 = f29_neg(b.c1);
-#pragma unroll
-  for (int i = 0; i < 9; i++)
-#pragma unroll
-    for (int j = 0; j < 9; j++) {
-      const bool set = FIRST && (i == 0 || j == 8);
-      w.re[i + j] = (set ? 0 : w.re[i + j]) + (int64_t)a.c0.l[i] * b.c0.l[j];
-      w.re[i + j] += (int64_t)a.c1.l[i] * nb1.l[j];
-      w.im[i + j] = (set ? 0 : w.im[i + j]) + (int64_t)a.c0.l[i] * b.c1.l[j];
-      w.im[i + j] += (int64_t)a.c1.l[i] * b.c0.l[j];
-    }
-}
-FTS_HD void w29_mac(W29& w, const q2& a, const q2& b) { w29_mac_t<false>(w, a, b); }
-FTS_HD void w29_set(W29& w, const q2& a, const q2& b) { w29_mac_t<true>(w, a, b); }
-#endif
 // Montgomery reduction of one row, balanced digits and result.  ADD: the value
 // row / R + f, f's limbs joining columns 9..17 (R f) ahead of the tail sweep --
 // limbs 0..7 of the sum come out balanced, limb 8 takes the signed rest
@@ -145,7 +115,6 @@ FTS_HD f29 w29_redc_t(int64_t c[17], const f29& f) {
   return r;
 }
 FTS_HD f29 w29_redc(int64_t c[17]) { return w29_redc_t<false>(c, f29{}); }
-#if FTS_SX_KARA
 FTS_HD q2 w29_reduce(W29& w) {
   int64_t re[17], im[17];
 #pragma unroll
@@ -165,26 +134,6 @@ FTS_HD q2 w29_reduce_add(W29& w, const q2& f) {
   }
   return {w29_redc_t<true>(re, f.c0), w29_redc_t<true>(im, f.c1)};
 }
-#else
-FTS_HD q2 w29_reduce(W29& w) { return {w29_redc(w.re), w29_redc(w.im)}; }
-FTS_HD q2 w29_reduce_add(W29& w, const q2& f) {
-  return {w29_redc_t<true>(w.re, f.c0), w29_redc_t<true>(w.im, f.c1)};
-}
-// w += s^2 (s balanced) as (s0 + s1)(s0 - s1) + 2 s0 s1 u: two limb-product rows
-// instead of the four of w29_mac(w, s, s)
-FTS_HD void w29_sqr_acc(W29& w, const q2& s) {
-  FTS_COUNT_MAD(128);
-  FTS_SCHED_FENCE();
-  const f29 p = f29_add(s.c0, s.c1), d = f29_sub(s.c0, s.c1), t = f29_add(s.c0, s.c0);
-#pragma unroll
-  for (int i = 0; i < 9; i++)
-#pragma unroll
-    for (int j = 0; j < 9; j++) {
-      w.re[i + j] += (int64_t)p.l[i] * d.l[j];
-      w.im[i + j] += (int64_t)t.l[i] * s.c1.l[j];
-    }
-}
-#endif
 
 // one Fp2 product a b (a, b limbs within 2^29), Karatsuba by columns: each
 // column's three sums U_c, V_c, W_c are formed and folded into re_c = U_c - V_c,
@@ -291,10 +240,6 @@ FTS_HD q2 sq_mulv(const X& x, const q2& a, const q2& b) {
   return sq_mul(x, a);
 }
 
-#ifndef FTS_SX_CYC2
-#define FTS_SX_CYC2 1
-#endif
-#if FTS_SX_CYC2
 // Granger-Scott cyclotomic squaring (as sx_cyc_sqr) with ONE Fp2 product per
 // lane.  The Fp4 pairs are (a_p, a_(p+3)); pair p's even lane (k = 2p) needs
 // a_p^2 + xi a_(p+3)^2, its odd lane (k = 3, 5, 1 for p = 0, 1, 2) the cross
@@ -306,7 +251,7 @@ FTS_HD q2 sq_mulv(const X& x, const q2& a, const q2& b) {
 // (each a four-term linear map, f29_lin4).  The even lane's operands are
 // unreduced sums (limbs within 2^29: one product, 18 limb products of <= 2^58
 // per column).  Versus one general product plus one complex square per lane:
-// 3 x 81 limb products instead of 3 x 81 + 3 x 45.
+// 3 x 81 limb products instead of 3 x 81 + 3 x 45 (profiles/r05/cyc2_ab.txt).
 template <class X>
 FTS_HD q2 sq_cyc_sqr(X x, q2 a) {
   const int k = x.k, odd = k & 1;
@@ -328,31 +273,6 @@ FTS_HD q2 sq_cyc_sqr(X x, q2 a) {
   int32_t b1 = odd ? (k == 1 ? 6 : 0) : -3, g1 = odd ? (k == 1 ? 54 : 6) : -30;
   return {f29_lin4(r.c0, cr, q.c0, b0, q.c1, g0, a.c0, ca), f29_lin4(r.c1, cr, q.c0, b1, q.c1, g1, a.c1, ca)};
 }
-#else
-// Granger-Scott cyclotomic squaring (as sx_cyc_sqr): even lanes 3 r - 2 a,
-// odd lanes 6 r + 2 a, r the lane's one or two products.  Every lane runs one
-// general product (even lanes a_{m+3} (xi a_{m+3}), odd lanes their cross
-// product) and one complex squaring (even lanes a_m^2, odd lanes of zero): six
-// limb-product rows per lane instead of two general products' eight.
-template <class X>
-FTS_HD q2 sq_cyc_sqr(X x, q2 a) {
-  const int k = x.k, m = k >> 1;
-  a = sq_pub(x, SX_A, a);
-  x.sync();
-  bool odd = (k & 1) != 0;
-  int i1 = odd ? (k == 1 ? 5 : (k == 3 ? 3 : 4)) : m + 3;
-  int j1 = odd ? (k == 1 ? SX_AX + 2 : (k == 3 ? SX_A + 0 : SX_A + 1)) : SX_AX + m + 3;
-  W29 w;
-  w29_init(w);
-  w29_mac(w, x.get(SX_A + i1), x.get(j1));
-  w29_sqr_acc(w, q2_sel(odd, q2_zero(), x.get(SX_A + m)));
-  x.sync();
-  q2 r = w29_reduce(w);
-  const int32_t cr = odd ? 6 : 3, ca = odd ? 2 : -2;
-  return {f29_lin2(r.c0, cr, a.c0, ca), f29_lin2(r.c1, cr, a.c1, ca)};
-}
-
-#endif
 
 FTS_HD q2 sq_conj(int k, const q2& a) { return (k & 1) ? q2_neg(a) : a; }
 FTS_HD q2 sq_frob1(int k, const q2& a) { return q2_mul(q2_conj(a), q2_from_fp2(f2_const(FROB1[k]))); }
@@ -379,9 +299,6 @@ FTS_HD q2 sq_expt(X x, const P& pk, int src, int ps) {
 #pragma nounroll
   for (int i = 61; i >= 0; i--) {
     r = sq_cyc_sqr(x, r);
-    // in the 18-slot layout the multiplier's slots alias SX_AX, which the
-    // squaring overwrites: republish before every multiplication
-    if (X::B == SX_AX) cur = 0;
     if ((BN_X_W4_NZ >> i) & 1) {
       int m = ((BN_X_W4_M3 >> i) & 1) ? 3 : (((BN_X_W4_M5 >> i) & 1) ? 5 : (((BN_X_W4_M7 >> i) & 1) ? 7 : 1));
       if (m != cur) {
@@ -482,7 +399,7 @@ struct Park {
 
 // Exact final exponentiation f^((p^12-1)/r) (Scott et al. chain, as
 // final_exp_exact in pairing.h) in three phases that the device runs as
-// separate kernels (k_fexp_easy, k_fexp_expt x 3, k_fexp_hard): composed in
+// separate kernels (the easy part's, k_fexp_expt x 3, k_fexp_hard): composed in
 // one kernel the phases' register needs (171, 236 and ~200 VGPRs alone) did not
 // fit together under the 256 of two waves per SIMD -- the compiler spilled
 // 340 VGPRs (1 KB per lane) and the kernel moved ~26x its algorithmic bytes.
@@ -593,7 +510,7 @@ FTS_HD fp2 sq_final_exp_exact(const X& x, const fp2& f, const P& pk) {
 }
 
 // Fuentes-Castaneda multiple (the selectable FTZ_FEXP_FUENTES variant), phased
-// like the exact one (k_fexp_easy, k_fexp_expt, k_fexp_fc_mid1, k_fexp_expt,
+// like the exact one (the easy part, k_fexp_expt, k_fexp_fc_mid1, k_fexp_expt,
 // k_fexp_fc_mid2, k_fexp_expt, k_fexp_fc_hard).  Slots: 0 t (easy part), 1 a =
 // t^x, 2 a2, 3 a6, 4 b = a6^x, 5 b^2, 6 c = (b^2)^x; the x-powers' odd powers
 // in FC_EXPT_SLOT ..+2.
@@ -650,29 +567,11 @@ FTS_HD f29 f29_mulb(const f29& a, const f29& b) {
   return w29_redc(c);
 }
 
-#if FTS_SX_KARA
-// the Karatsuba rows take the same three squarings as w29_sqr_acc
+// w += s^2 for sq_sqr: the three squarings of w29_sqr_acc
 FTS_HD void w29_sqr3_acc(W29& w, const q2& s) {
-  FTS_COUNT_MAD(32);  // the schoolbook variant's count (160), for opcounts
+  FTS_COUNT_MAD(32);  // with w29_sqr_acc's 128 the schoolbook count (160), for opcounts
   w29_sqr_acc(w, s);
 }
-#else
-// w += s^2 (s balanced) as s0 s0 - s1 s1 + (2 s0) s1 u: three limb-product rows
-// (the column bound stays that of w29_mac(w, s, s): 18 units of 2^56 per row)
-FTS_HD void w29_sqr3_acc(W29& w, const q2& s) {
-  FTS_COUNT_MAD(160);
-  FTS_SCHED_FENCE();
-  const f29 t = f29_add(s.c0, s.c0), n1 = f29_neg(s.c1);
-#pragma unroll
-  for (int i = 0; i < 9; i++)
-#pragma unroll
-    for (int j = 0; j < 9; j++) {
-      w.re[i + j] += (int64_t)s.c0.l[i] * s.c0.l[j];
-      w.re[i + j] += (int64_t)s.c1.l[i] * n1.l[j];
-      w.im[i + j] += (int64_t)t.l[i] * s.c1.l[j];
-    }
-}
-#endif
 
 // c = a^2 (as sx_sqr): a, xi a and 2 a published (2 a unreduced: its limbs
 // are within 2^29 and SX_SQR4_TAB gives every lane at most 6 operand units).
@@ -702,7 +601,10 @@ FTS_HD q2 sq_sqr(X x, q2 a) {
   return w29_reduce(w);
 }
 
-// f * (l0 + l1 w + l3 w^3), the line in registers of every lane (as sx_mul_line_r)
+// f * (l0 + l1 w + l3 w^3), the line in registers of every lane (as
+// sx_mul_line_r).  The Miller loops load a pair-2 line's three coefficients
+// before the product: that hides the load latency, and reading them one at a
+// time inside the term loop was not faster (no record kept).
 template <class X>
 FTS_HD q2 sq_mul_line_r(const X& x, const q2& f, const q2& l0, const q2& l1, const q2& l3) {
   sq_pub(x, SX_A, f);
@@ -714,29 +616,6 @@ FTS_HD q2 sq_mul_line_r(const X& x, const q2& f, const q2& l0, const q2& l1, con
     int j = x.k - (t == 1 ? 1 : 3);
     int sb = j < 0 ? SX_AX + j + 6 : SX_A + j;
     w29_mac(w, t == 1 ? l1 : l3, x.get(sb));
-  }
-  x.sync();
-  return w29_reduce(w);
-}
-
-// f * (pair-2 line s), the three evaluated coefficients read from the line
-// buffer inside the term loop, one at a time (FTS_MILLER_EVLINE_IN_LOOP; the
-// default loads all three before the product, sq_mul_line_r, which hides the
-// load latency and fits the registers since the multiplicands are pinned)
-#ifndef FTS_MILLER_EVLINE_IN_LOOP
-#define FTS_MILLER_EVLINE_IN_LOOP 0
-#endif
-template <class X>
-FTS_HD q2 sq_mul_evline(const X& x, const q2& f, const EvLineDev* l2, uint32_t s, uint32_t idx, uint32_t njobs) {
-  sq_pub(x, SX_A, f);
-  x.sync();
-  W29 w;
-  w29_set(w, evline_ld29(l2, s, 0, idx, njobs), x.get(SX_A + x.k));
-#pragma nounroll
-  for (int t = 1; t < 3; t++) {
-    int j = x.k - (t == 1 ? 1 : 3);
-    int sb = j < 0 ? SX_AX + j + 6 : SX_A + j;
-    w29_mac(w, evline_ld29(l2, s, t, idx, njobs), x.get(sb));
   }
   x.sync();
   return w29_reduce(w);
@@ -900,12 +779,8 @@ FTS_HD q2 sq_miller_fn(const X& x, const LineCoef29* qlines_n, const g1a& P1, co
     bool sq = s < 64 ? ((MILLER_SQR.lo >> s) & 1) : ((MILLER_SQR.hi >> (s - 64)) & 1);
     if (sq) f = sq_sqr(x, f);
     f = sq_fixed_line_n(x, f, qlines_n[s], xq, yi, P1.inf);
-#if FTS_MILLER_EVLINE_IN_LOOP
-    f = sq_mul_evline(x, f, l2, s, idx, njobs);
-#else
     f = sq_mul_line_r(x, f, evline_ld29(l2, s, 0, idx, njobs), evline_ld29(l2, s, 1, idx, njobs),
                       evline_ld29(l2, s, 2, idx, njobs));
-#endif
   }
   return f;
 }
@@ -922,12 +797,8 @@ FTS_HD q2 sq_miller_f(const X& x, const LineCoef29* qlines, const g1a& P1, const
     bool sq = s < 64 ? ((MILLER_SQR.lo >> s) & 1) : ((MILLER_SQR.hi >> (s - 64)) & 1);
     if (sq) f = sq_sqr(x, f);
     f = sq_fixed_line(x, f, qlines[s], yP, xP, P1.inf);
-#if FTS_MILLER_EVLINE_IN_LOOP
-    f = sq_mul_evline(x, f, l2, s, idx, njobs);
-#else
     f = sq_mul_line_r(x, f, evline_ld29(l2, s, 0, idx, njobs), evline_ld29(l2, s, 1, idx, njobs),
                       evline_ld29(l2, s, 2, idx, njobs));
-#endif
   }
   return f;
 }
@@ -935,7 +806,7 @@ FTS_HD q2 sq_miller_f(const X& x, const LineCoef29* qlines, const g1a& P1, const
 // LDS dwords per sextet region: NS slots of 18 dwords, padded.  The operand
 // exchange is compiled to ds_read2_b64 / ds_read2_b32 / ds_write2_b64 /
 // ds_write2_b32, all of which bank on (a/4) mod 32 (MI355X_MICROARCH.md, LDS
-// table).  FTS_SQ_PAD (default 12): the region stride is = 12 mod 32 dwords.
+// table).  The region stride is = SQ_PAD_MOD32 = 12 mod 32 dwords.
 // A model of the exchange's access patterns (broadcast gets, per-lane slot
 // gets, per-lane puts; 16-lane groups for b64, 32-lane for b32; lane = 6
 // sextet + k; the x-power's cyclotomic squarings and products, the Miller
@@ -943,18 +814,13 @@ FTS_HD q2 sq_miller_f(const X& x, const LineCoef29* qlines, const g1a& P1, const
 // 2.6x and the Miller step at 1.4x fewer conflict cycles than the previous
 // rule, the best of every stride mod 32 and of slot strides 18..30 (measured,
 // 20 mod 32: k_fexp_expt 9.97 -> 3.34 conflict cycles per LDS instruction,
-// 746 -> 728 us; profiles/r06/lds_pad.txt).  FTS_SQ_PAD = 0: the previous
-// rule, distinct even banks mod 64 (stride = 2 x odd mod 64), which only the
-// b64 reads' banking (mod 64) would favour.
-#ifndef FTS_SQ_PAD
-#define FTS_SQ_PAD 12
-#endif
+// 746 -> 728 us; profiles/r06/lds_pad.txt).  The previous rule put the
+// regions on distinct even banks mod 64 (stride = 2 x odd mod 64), which only
+// the b64 reads' banking (mod 64) would favour.
+static constexpr uint32_t SQ_PAD_MOD32 = 12;
 constexpr uint32_t sq_region_dwords(uint32_t ns) {
   uint32_t s = ns * 18;
-  if (FTS_SQ_PAD)
-    while (s % 32 != FTS_SQ_PAD) s += 2;
-  else
-    while ((s % 64) % 4 != 2) s += 2;
+  while (s % 32 != SQ_PAD_MOD32) s += 2;
   return s;
 }
 

@@ -3,9 +3,9 @@
 8x8 -> 16 limb product and the 16 -> 8 limb Montgomery reduction, each as ONE
 inline-asm statement.
 
-The per-column statements of gen_fips.py / gen_wide.py leave C glue between
-columns (carry-word shifts, m_k = acc * inv, r_k = acc) and hipcc pads each
-statement boundary with an s_nop.  Here the 96-bit column accumulator lives in
+One asm statement per column leaves C glue between columns (carry-word
+shifts, m_k = acc * inv, r_k = acc) and hipcc pads each statement boundary
+with an s_nop.  Here the 96-bit column accumulator lives in
 fixed, clobbered registers: the 64-bit sum in one of the pairs v[0:1] / v[2:3]
 and the carry word in the odd register of the other pair, so that the shift
 acc >>= 32 at a column end is ONE v_mov into the other pair's even register

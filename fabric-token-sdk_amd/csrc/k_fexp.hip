@@ -10,8 +10,8 @@ using namespace fts;
 
 // Final exponentiations, sextet layout (see k_miller), carry-free 29-bit
 // accumulation (dev/sx29.h).  FTZ_FEXP_EXACT (the default) computes
-// f^((p^12-1)/r) in five launches -- k_fexp_easy, k_fexp_expt x 3, k_fexp_hard
-// -- that hand m, m^x, m^(x^2), m^(x^3) over in the park planes (Park,
+// f^((p^12-1)/r) in five phases -- the easy part (three launches, below),
+// k_fexp_expt x 3, k_fexp_hard -- that hand m, m^x, m^(x^2), m^(x^3) over in the park planes (Park,
 // fexp_park_bytes); FTZ_FEXP_FUENTES (the Fuentes-Castaneda multiple) in
 // seven (the same easy and x-power kernels plus k_fexp_fc_*).  All launches of
 // one pass use the same grid, so a lane's park index is the same in every
@@ -30,14 +30,7 @@ __device__ __forceinline__ fp2 fexp_load(const F12Dev* fin, uint32_t idx, int k)
   return f;
 }
 
-// phase 1: easy part, m -> park slot 0
-__global__ void __launch_bounds__(64, 2) k_fexp_easy(uint32_t n, const F12Dev* fbuf, int32_t* park) {
-  SQ_KERNEL_PROLOGUE(n, SX_SLOTS_FEXP)
-  FEXP_PARK
-  pk.put(0, sq_fexp_easy(x, fexp_load(fbuf, jc, x.k)));
-}
-
-// phase 1 in three launches (the device default): the easy part with the
+// phase 1 in three launches: the easy part, m -> park slot 0, with the
 // launch's Fp inversions batched (dev/sx29.h sq_fexp_easy_a / _b)
 __global__ void __launch_bounds__(64, 2) k_fexp_easy_a(uint32_t n, const F12Dev* fbuf, int32_t* park) {
   SQ_KERNEL_PROLOGUE(n, SX_SLOTS_FEXP)
@@ -65,21 +58,10 @@ __global__ void __launch_bounds__(256) k_fexp_binv(uint32_t n, int32_t* park, ui
 // phase 2 (three launches): slot dst = (slot src)^x, a^3, a^5, a^7 parked
 // from slot ps (a is re-read from src).  24 LDS slots (A, AX, B, BX): 17.4 KB
 // per workgroup, so LDS admits the two waves per SIMD that the registers allow
-// (the 30-slot region's 21.7 KB admitted 1.75).
-#ifndef FTS_EXPT_SLOTS
-#define FTS_EXPT_SLOTS 24
-#endif
-#if FTS_EXPT_SLOTS == 18
-// 18 LDS slots (A, AX = B, BX: the multiplier republished after every
-// squaring), 13 KB per workgroup: LDS admits three waves per SIMD, but the
-// 168 VGPRs of three waves spill (164 B per lane) and the launch ran 4.02-4.06
-// against 3.56-3.58 ms per 8192-proof pass (profiles/r05/expt_slots_ab.txt)
-__global__ void __launch_bounds__(64, 3) k_fexp_expt(uint32_t n, int32_t* park, int src, int dst, int ps) {
-  SQ_KERNEL_PROLOGUE_B(n, 18, 6)
-#else
+// (the 30-slot region's 21.7 KB admitted 1.75; 18 slots for three waves per
+// SIMD spilled and ran slower: profiles/r05/expt_slots_ab.txt).
 __global__ void __launch_bounds__(64, 2) k_fexp_expt(uint32_t n, int32_t* park, int src, int dst, int ps) {
   SQ_KERNEL_PROLOGUE_B(n, 24, 12)
-#endif
   FEXP_PARK
   pk.put(dst, sq_expt(x, pk, src, ps));
 }

@@ -5,13 +5,6 @@
 #include "dev/jobs.h"
 #include "launch.h"
 
-#ifndef FTS_G1PART_PRIO
-#define FTS_G1PART_PRIO 0  // wave priority of k_g1_part (A/B)
-#endif
-#ifndef FTS_COMBINE_PRIO
-#define FTS_COMBINE_PRIO FTS_BINV_PRIO  // wave priority of the block inversion's Euclid (dev/binv.h)
-#endif
-
 using namespace fts;
 
 #define JOB_KERNEL_PROLOGUE(n)                          \
@@ -36,9 +29,6 @@ __global__ void __launch_bounds__(128) k_g1_part(const G1Job* jobs, uint32_t n, 
     if (lane - vbase >= nvl) return;
     i = vlist[lane - vbase];
   }
-#if FTS_G1PART_PRIO
-  __builtin_amdgcn_s_setprio(FTS_G1PART_PRIO);
-#endif
   job_g1_part(jobs, n, i, vt, pts, scal, tab, part, vtab);
 }
 
@@ -81,7 +71,7 @@ __device__ fp block_batch_inv(fp x, uint32_t (*pre)[NT], uint32_t (*suf)[NT], ui
     fp all;
 #pragma unroll
     for (int k = 0; k < 8; k++) all.v[k] = pre[k][NT - 1];
-    __builtin_amdgcn_s_setprio(FTS_COMBINE_PRIO);  // the block waits on this wave
+    __builtin_amdgcn_s_setprio(LONE_INV_PRIO);  // the block waits on this wave
     fp ia = fp_inv_var(all);  // public values; one wave, one value: no divergence
     __builtin_amdgcn_s_setprio(0);
     if (t == 0)

@@ -9,15 +9,8 @@
 
 using namespace fts;
 
-#ifndef FTS_G2_PART_X29
-#define FTS_G2_PART_X29 1
-#endif
 #ifndef FTS_G2_PART_WAVES
 #define FTS_G2_PART_WAVES 1  // waves per SIMD k_g2_part is compiled for
-#endif
-
-#ifndef FTS_G2LINES_PRIO
-#define FTS_G2LINES_PRIO 0  // wave priority of k_g2lines1 (A/B)
 #endif
 
 #define JOB_KERNEL_PROLOGUE(n)                          \
@@ -40,9 +33,9 @@ __global__ void __launch_bounds__(64, 2) k_g2lines(const G2Job* g2, const PairJo
   sx_job_g2lines(x, g2[jc], pr[jc], scal, tab, g2out, pts, lines, jc, n, valid);
 }
 
-// The same in the one-lane layout, split (job_g2_part / job_g2lines_parts):
-// FTS_G2_PART_X29 (default 1) sums the parts in the carry-free XYZZ form
-// (dev/g2x29.h), 0 in the 32-bit Jacobian one.
+// The same in the one-lane layout, split: the parts are summed in the
+// carry-free XYZZ form (dev/g2x29.h; against the 32-bit Jacobian sum,
+// job_g2_part: profiles/r05/g2_part_x29_ab.txt);
 // four lanes per job sum the table points (part-major, so every wave runs one
 // part), then one lane per job adds the partials and emits the lines.
 __global__ void __launch_bounds__(64, FTS_G2_PART_WAVES) k_g2_part(const G2Job* g2, uint32_t n, const uint32_t (*scal)[8],
@@ -50,15 +43,12 @@ __global__ void __launch_bounds__(64, FTS_G2_PART_WAVES) k_g2_part(const G2Job* 
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * n) return;
   uint32_t q = i / n, job = i - q * n;
-#if FTS_G2_PART_X29
   job_g2_part_x29(g2[job], (int)q, scal, tab, part[i]);
-#else
-  job_g2_part(g2[job], (int)q, scal, tab, part[i]);
-#endif
 }
-// FTS_G2_BINV (default 1): the partial sums added in k_g2_sum and the
-// launch's inversions batched (k_g2_binv) before k_g2lines1, instead of one
-// inversion per lane inside it (X29 line chain only)
+// The partial sums are added in k_g2_sum and the launch's inversions batched
+// (k_g2_binv) before k_g2lines1, instead of one inversion per lane inside it
+// (profiles/r05/g2_binv_ab.txt); the line chain runs on the carry-free form
+// (dev/g2lines29.h; against the 32-bit chain: profiles/r05/g2lines_x29_ab.txt)
 __global__ void __launch_bounds__(64) k_g2_sum(uint32_t n, G2PartDev* part) {
   JOB_KERNEL_PROLOGUE(n);
   job_g2_sum(part, i, n);
@@ -84,16 +74,7 @@ __global__ void __launch_bounds__(64) k_g2lines1(const G2Job* g2, const PairJob*
                                                  const G2PartDev* part, G2Dev* g2out, const G1Dev* pts,
                                                  EvLineDev* lines) {
   JOB_KERNEL_PROLOGUE(n);
-#if FTS_G2LINES_PRIO
-  __builtin_amdgcn_s_setprio(FTS_G2LINES_PRIO);
-#endif
-#if FTS_G2LINES_X29 && FTS_G2_BINV
   job_g2lines_summed_x29(g2[i], pr[i], part, g2out, pts, lines, i, n);
-#elif FTS_G2LINES_X29
-  job_g2lines_parts_x29(g2[i], pr[i], part, g2out, pts, lines, i, n);
-#else
-  job_g2lines_parts(g2[i], pr[i], part, g2out, pts, lines, i, n);
-#endif
 }
 
 // ---- wide-window G2 tables (C > 8), as k_tab_g1_bw / k_tab_g1_fill

@@ -74,12 +74,6 @@ __global__ void k_g2(const G2Job* jobs, uint32_t n, const uint32_t (*scal)[8], c
 __global__ void k_g2lines(const G2Job* g2, const PairJob* pr, uint32_t n, const uint32_t (*scal)[8], const G2Dev* tab,
                           G2Dev* g2out, const G1Dev* pts, EvLineDev* lines);
 __global__ void k_g2_part(const G2Job* g2, uint32_t n, const uint32_t (*scal)[8], const G2Dev* tab, G2PartDev* part);
-#ifndef FTS_G2LINES_X29
-#define FTS_G2LINES_X29 1  // k_g2lines1's line chain on the carry-free form (dev/g2lines29.h)
-#endif
-#ifndef FTS_G2_BINV
-#define FTS_G2_BINV 1  // k_g2_sum + k_g2_binv before k_g2lines1 (k_g2.hip)
-#endif
 __global__ void k_g2_sum(uint32_t n, G2PartDev* part);
 __global__ void k_g2_binv(uint32_t n, G2PartDev* part);
 __global__ void k_g2lines1(const G2Job* g2, const PairJob* pr, uint32_t n, const G2PartDev* part, G2Dev* g2out,
@@ -95,12 +89,9 @@ __global__ void k_miller_n(const PairJob* jobs, uint32_t n, const LineCoef29* ql
 __global__ void k_miller_f3(const PairJob* jobs, uint32_t n, const LineCoef29* qlines_n, const LineCoef29* pklines_n,
                             const G1Dev* g1out, const G1Dev* pnorm, F12Dev* fbuf);
 // final exponentiation phases (k_fexp.hip); park: fexp_park_bytes(n) of scratch (dev/sx29.h Park).
-// FTS_FEXP_EASY_BATCH (default 1): the easy part in three launches with the
-// launch's Fp inversions batched (k_fexp_easy_a, k_fexp_binv, k_fexp_easy_b)
-#ifndef FTS_FEXP_EASY_BATCH
-#define FTS_FEXP_EASY_BATCH 1
-#endif
-__global__ void k_fexp_easy(uint32_t n, const F12Dev* fbuf, int32_t* park);
+// The easy part runs in three launches with the launch's Fp inversions batched
+// (k_fexp_easy_a, k_fexp_binv, k_fexp_easy_b; against one launch with an
+// inversion per sextet: profiles/r05/fexp_easy_batch_ab.txt)
 __global__ void k_fexp_easy_a(uint32_t n, const F12Dev* fbuf, int32_t* park);
 __global__ void k_fexp_easy_b(uint32_t n, const F12Dev* fbuf, int32_t* park);
 __global__ void k_fexp_binv(uint32_t n, int32_t* park, uint32_t stride);
@@ -118,13 +109,9 @@ inline void launch_fexp(bool exact, const PairJob* jobs, uint32_t n, const F12De
                         int32_t* park, hipStream_t s) {
   if (!n) return;
   const uint32_t nb = (n + SX_JOBS_PER_WAVE - 1) / SX_JOBS_PER_WAVE;
-#if FTS_FEXP_EASY_BATCH
   k_fexp_easy_a<<<nb, 64, 0, s>>>(n, fbuf, park);
   k_fexp_binv<<<(n + 255) / 256, 256, 0, s>>>(n, park, nb * 64);
   k_fexp_easy_b<<<nb, 64, 0, s>>>(n, fbuf, park);
-#else
-  k_fexp_easy<<<nb, 64, 0, s>>>(n, fbuf, park);
-#endif
   if (exact) {
     for (int e = 0; e < 3; e++) k_fexp_expt<<<nb, 64, 0, s>>>(n, park, e, e + 1, 4);
     k_fexp_hard<<<nb, 64, 0, s>>>(jobs, n, arena, park);
@@ -149,11 +136,9 @@ __global__ void k_msm_load_pts(uint32_t n, const uint8_t* raw_pts, G1Dev* pts, u
 __global__ void k_g1_sum(uint32_t n, const uint8_t* raw, uint8_t* out, uint32_t* status);
 __global__ void k_g1_check(uint32_t n, const uint8_t* slots, uint8_t* ok);
 __global__ void k_msm_load_scal(uint32_t n, const uint8_t* raw_scal, uint32_t (*scal)[8]);
-__global__ void k_msm_keys(MsmPlan p, const uint32_t (*scal)[8], uint32_t* key, uint32_t* val, uint32_t* cnt);
-__global__ void k_msm_scatter(MsmPlan p, const uint32_t* key, const uint32_t* val, const uint32_t* start,
-                              uint32_t* cnt, uint32_t* perm);
+__global__ void k_msm_keys(MsmPlan p, const uint32_t (*scal)[8], uint32_t* key, uint32_t* val);
 __global__ void k_msm_keys_raw(MsmPlan p, uint32_t i0, uint32_t i1, const uint8_t* raw, uint32_t (*scal)[8],
-                               uint32_t* key, uint32_t* val, uint32_t* cnt);
+                               uint32_t* key, uint32_t* val);
 __global__ void k_msm_bounds(MsmPlan p, uint64_t total, const uint32_t* skey, const uint32_t* sval, uint32_t* start,
                              uint32_t* end);
 __global__ void k_scan_block(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tot);
@@ -175,8 +160,6 @@ __global__ void k_msm_bucket(MsmPlan p, const uint32_t* whi, const uint32_t* ord
 __global__ void k_msm_segment(MsmPlan p, uint32_t w0, uint32_t w1, const uint32_t* wlo, const uint32_t* whi,
                               const uint32_t* owner, const G1JDev* slot_sum, G1JDev* part);
 __global__ void k_msm_tree(const G1JDev* in, uint32_t m, G1JDev* out);
-__global__ void k_msm_horner(MsmPlan p, uint32_t w_hi, uint32_t w_lo, const G1JDev* wparts, uint32_t per,
-                             G1JDev* acc_buf);
 __global__ void k_msm_genpoints(uint32_t n, uint32_t off, uint32_t chunk, const G1Dev* gtab, G1JDev* jtmp,
                                 uint32_t (*zs)[8], G1Dev* pts);
 

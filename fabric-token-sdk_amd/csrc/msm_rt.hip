@@ -24,7 +24,6 @@ struct ftz_msm {
   size_t sort_tmp_bytes = 0;
   uint32_t key_bits = 0;
   DBuf<G1JDev> slot_sum, part, tree;
-  DBuf<G1JDev> hacc;
   G1JDev* hwin = nullptr;  // page-locked: the window sums read back for the host Horner
   DBuf<uint8_t> ok;
   hipEvent_t ev[2];
@@ -45,15 +44,6 @@ struct ftz_msm {
   hipGraphExec_t graph_exec = nullptr;
   int graph_state = 0;
   uint32_t radix_bits = 8;  // digit bits per radix-sort pass (8: rocPRIM's gfx950 default; 9: Radix9)
-  // FTS_MSM_CSORT=1, small plans (dev/msm.h MSM_SMALL_LG): a counting sort
-  // instead of rocPRIM's radix sort -- the keys kernel counts each (window,
-  // bucket) group with an atomic, a scan gives the group starts, one scatter
-  // places the values by returning atomics (end[] holds the counts).  It
-  // saves ~9 of the radix sort's and bounds pass's ~5 us dependent launches
-  // but measured slower from 2^16 points up (2^16 0.71 against 0.61-0.64 ms,
-  // 2^18 1.66 against 1.16-1.19: the scatter's 1.3M returning atomics take
-  // 95 us), faster only at 2^14 (0.51 against 0.56), profiles/r06/msm_csort.txt
-  bool csort = false;
 };
 
 static int blocks(uint64_t n, int bs) { return (int)((n + bs - 1) / bs); }
@@ -62,7 +52,9 @@ static int blocks(uint64_t n, int bs) { return (int)((n + bs - 1) / bs); }
 // pass) or, where 9-bit digits save a pass (17- and 18-bit keys: 2^24 points at
 // c = 19), the same kernel shape with 512 digit bins.  An 11-bit config (2048
 // digit bins, 256-thread blocks, match ranking) measured slower in round 3:
-// 2^20 3.29 -> 4.33 ms, 2^24 29.0 -> 44.6 ms.
+// 2^20 3.29 -> 4.33 ms, 2^24 29.0 -> 44.6 ms.  A counting sort for small plans
+// (atomic group counts, a scan, one scatter) measured slower from 2^16 points
+// up (profiles/r06/msm_csort.txt).
 using Radix9 = rocprim::radix_sort_config<
     rocprim::default_config, rocprim::default_config,
     rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 12>, rocprim::kernel_config<1024, 12>, 9,
@@ -89,10 +81,6 @@ static int msm_alloc(ftz_msm* m, size_t n) {
   m->end_p = m->zb.p + wb;
   m->lenhist_p = m->zb.p + 2 * wb;
   m->key_bits = msm_key_bits(p);
-#ifndef FTS_MSM_CSORT
-#define FTS_MSM_CSORT 0
-#endif
-  m->csort = FTS_MSM_CSORT && !p.pre && msm_lg(p.nv) <= MSM_SMALL_LG;
   // 9-bit digits where they save a pass (17-18 bits: two passes instead of three)
   if (p.rw > 32) return set_err(FTZ_E_INVALID, "MSM plan has more than 32 windows");
   const uint32_t rb = m->ctx->opt.msm_radix_bits;
@@ -108,7 +96,6 @@ static int msm_alloc(ftz_msm* m, size_t n) {
   HC(m->order.alloc(ws));
   HC(m->part.alloc((size_t)p.rw * p.segs));
   HC(m->tree.alloc((size_t)p.rw * ((p.segs + MSM_TREE_CHUNK - 1) / MSM_TREE_CHUNK) * 2));
-  HC(m->hacc.alloc(1));
   HC(hipHostMalloc(reinterpret_cast<void**>(&m->hwin), (size_t)p.rw * sizeof(G1JDev), hipHostMallocDefault));
   HC(m->ok.alloc(n));
   for (int k = 0; k < 2; k++) HC(hipEventCreate(&m->ev[k]));
@@ -265,33 +252,23 @@ static int msm_enqueue_tail(ftz_msm* m, hipStream_t s) {
   const MsmPlan& p = m->p;
   size_t wb = (size_t)p.rw * p.buckets;
   size_t wn = (size_t)p.windows * p.nv;
-  int rc;
-  if (m->csort) {
-    // counting sort: end[] = the group counts from the keys kernel
-    rc = scan(m->end_p, m->start_p, wb, m->tot.p, s);
-    if (rc != FTZ_SUCCESS) return rc;
-    k_msm_counts_scan<<<blocks(wb, 1024), 1024, 0, s>>>(p, nullptr, m->end_p, m->count.p, m->soff.p, m->tot.p);
-    k_msm_scatter<<<blocks(p.n, 256), 256, 0, s>>>(p, m->key.p, m->val.p, m->start_p, m->end_p, m->perm.p);
-  } else {
-    // (window, bucket)-sorted point lists: stable radix sort, bucket ranges
-    size_t tb = m->sort_tmp_bytes;
-    HC(msm_sort(m, m->sort_tmp.p, tb, wn, s));
-    HC(hipMemsetAsync(m->zb.p, 0, (2 * wb + 1024) * sizeof(uint32_t), s));  // start, end, histogram
-    k_msm_bounds<<<blocks(wn, 256), 256, 0, s>>>(p, (uint64_t)wn, m->skey.p, m->perm.p, m->start_p, m->end_p);
-    k_msm_counts_scan<<<blocks(wb, 1024), 1024, 0, s>>>(p, m->start_p, m->end_p, m->count.p, m->soff.p, m->tot.p);
-  }
+  // (window, bucket)-sorted point lists: stable radix sort, bucket ranges
+  size_t tb = m->sort_tmp_bytes;
+  HC(msm_sort(m, m->sort_tmp.p, tb, wn, s));
+  HC(hipMemsetAsync(m->zb.p, 0, (2 * wb + 1024) * sizeof(uint32_t), s));  // start, end, histogram
+  k_msm_bounds<<<blocks(wn, 256), 256, 0, s>>>(p, (uint64_t)wn, m->skey.p, m->perm.p, m->start_p, m->end_p);
+  k_msm_counts_scan<<<blocks(wb, 1024), 1024, 0, s>>>(p, m->start_p, m->end_p, m->count.p, m->soff.p, m->tot.p);
   // the slot-count scan's higher levels (its first level ran fused above)
   const uint32_t nb = (uint32_t)((wb + 1023) / 1024);
   if (nb > 1) {
     uint32_t* sums = m->tot.p + nb;
-    rc = scan(m->tot.p, sums, nb, sums + nb + 1, s);
+    int rc = scan(m->tot.p, sums, nb, sums + nb + 1, s);
     if (rc != FTZ_SUCCESS) return rc;
     k_scan_add<<<nb, 1024, 0, s>>>(m->soff.p, (uint32_t)wb, sums);
   }
   k_msm_owner<<<blocks(wb, 256), 256, 0, s>>>(p, m->count.p, m->soff.p, m->owner.p, m->wlo.p, m->whi.p);
   // bucket slots in length order, then one lane per slot
   size_t sl = (size_t)p.rw * p.max_slots;
-  if (m->csort) HC(hipMemsetAsync(m->lenhist_p, 0, 1024 * sizeof(uint32_t), s));
   k_msm_len_hist<<<blocks(sl, 256), 256, 0, s>>>(p, m->whi.p, m->owner.p, m->soff.p, m->count.p, m->lenhist_p);
   k_msm_len_scan<<<1, 1024, 0, s>>>(p, m->lenhist_p);
   k_msm_len_scatter<<<blocks(sl, 256), 256, 0, s>>>(p, m->whi.p, m->owner.p, m->soff.p, m->count.p,
@@ -301,14 +278,11 @@ static int msm_enqueue_tail(ftz_msm* m, hipStream_t s) {
   k_msm_segment<<<blocks((size_t)p.rw * p.segs, MSM_SEG_PER_BLOCK), MSM_SEG_THREADS, 0, s>>>(p, 0, p.rw, m->wlo.p, m->whi.p,
                                                                        m->owner.p, m->slot_sum.p, m->part.p);
   // tree passes: segs -> ceil(segs / chunk) -> ... until one part per window
-  // (host Horner) or at most HORNER_PARTS, which the Horner wave adds up itself
-  // (quads in parallel)
-  const uint32_t HORNER_PARTS = FTS_MSM_HOST_HORNER ? 1 : 8;
   G1JDev* bufs[2] = {m->tree.p, m->tree.p + (size_t)p.rw * ((p.segs + MSM_TREE_CHUNK - 1) / MSM_TREE_CHUNK)};
   const G1JDev* in = m->part.p;
   uint32_t cnt = p.segs;
   int which = 0;
-  while (cnt > HORNER_PARTS) {
+  while (cnt > 1) {
     uint32_t chunks = (cnt + MSM_TREE_CHUNK - 1) / MSM_TREE_CHUNK;
     G1JDev* out = bufs[which];
     k_msm_tree<<<p.rw * chunks, 256, 0, s>>>(in, cnt, out);
@@ -316,11 +290,7 @@ static int msm_enqueue_tail(ftz_msm* m, hipStream_t s) {
     which ^= 1;
     cnt = chunks;
   }
-#if FTS_MSM_HOST_HORNER
   HC(hipMemcpyAsync(m->hwin, in, (size_t)p.rw * sizeof(G1JDev), hipMemcpyDeviceToHost, s));
-#else
-  k_msm_horner<<<1, 64, 0, s>>>(p, p.rw, 0, in, cnt, m->hacc.p);
-#endif
   return FTZ_SUCCESS;
 }
 
@@ -328,8 +298,8 @@ static int msm_enqueue_tail(ftz_msm* m, hipStream_t s) {
 // the pipeline read back (rw * 96 bytes): c (rw - 1) dependent doublings (120 at
 // 2^16 and 2^20) are one serial chain whatever the device does, and a host core
 // runs a doubling in 4x64-bit Montgomery limbs (FTS_HOST64) several times faster
-// than one wave's latency-bound chain (k_msm_horner: 284-298 us per MSM,
-// profiles/r06/msm_trace.txt) -- the split sppark's Pippenger also makes.  The
+// than one wave's latency-bound chain (the device chain lost:
+// profiles/r06/msm_tail.txt) -- the split sppark's Pippenger also makes.  The
 // affine result is unique, so the bytes are those of the device chain.
 // Counted in last_ms.
 static fts::g1j msm_horner_host(const MsmPlan& p, const G1JDev* win) {
@@ -352,19 +322,10 @@ static int msm_finish(ftz_msm* m, uint8_t out[64]) {
   hipStream_t s = m->ctx->stream;
   HC(hipEventRecord(m->ev[1], s));
   HC(hipGetLastError());
-#if FTS_MSM_HOST_HORNER
   HC(hipStreamSynchronize(s));
+  // Horner, affine conversion and RawBytes on the host; counted in last_ms
   auto t0 = std::chrono::steady_clock::now();
   fts::g1j_to_raw(msm_horner_host(m->p, m->hwin), out);
-#else
-  G1JDev acc;
-  HC(hipMemcpyAsync(&acc, m->hacc.p, sizeof(acc), hipMemcpyDeviceToHost, s));
-  HC(hipStreamSynchronize(s));
-  // affine conversion + RawBytes on the host (one inverse: a few microseconds
-  // here, ~40k single-lane instructions on the device); counted in last_ms
-  auto t0 = std::chrono::steady_clock::now();
-  fts::g1j_to_raw(fts::g1j_load(acc), out);
-#endif
   double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   HC(hipEventElapsedTime(&m->last_ms, m->ev[0], m->ev[1]));
   m->last_ms += (float)host_ms;
@@ -374,8 +335,7 @@ static int msm_finish(ftz_msm* m, uint8_t out[64]) {
 static int msm_enqueue_all(ftz_msm* m, hipStream_t s) {
   const MsmPlan& p = m->p;
   const uint32_t(*scal)[8] = reinterpret_cast<const uint32_t(*)[8]>(m->scal.p);
-  if (m->csort) HC(hipMemsetAsync(m->end_p, 0, (size_t)p.rw * p.buckets * sizeof(uint32_t), s));
-  k_msm_keys<<<blocks(p.n, 256), 256, 0, s>>>(p, scal, m->key.p, m->val.p, m->csort ? m->end_p : nullptr);
+  k_msm_keys<<<blocks(p.n, 256), 256, 0, s>>>(p, scal, m->key.p, m->val.p);
   return msm_enqueue_tail(m, s);
 }
 
@@ -444,7 +404,6 @@ extern "C" int ftz_msm_run_scalars(ftz_msm* m, const uint8_t* scalars, uint8_t o
   HC(hipStreamWaitEvent(m->cstream, m->cev[ftz_msm::RAW_CHUNKS], 0));
   HC(hipEventRecord(m->ev[0], m->cstream));
   uint32_t(*scal)[8] = reinterpret_cast<uint32_t(*)[8]>(m->scal.p);
-  if (m->csort) HC(hipMemsetAsync(m->end_p, 0, (size_t)p.rw * p.buckets * sizeof(uint32_t), s));
   const uint32_t per = (p.n + ftz_msm::RAW_CHUNKS - 1) / ftz_msm::RAW_CHUNKS;
   for (int k = 0; k < ftz_msm::RAW_CHUNKS; k++) {
     uint32_t i0 = k * per, i1 = std::min<uint32_t>(p.n, i0 + per);
@@ -453,8 +412,7 @@ extern "C" int ftz_msm_run_scalars(ftz_msm* m, const uint8_t* scalars, uint8_t o
                       hipMemcpyHostToDevice, m->cstream));
     HC(hipEventRecord(m->cev[k], m->cstream));
     HC(hipStreamWaitEvent(s, m->cev[k], 0));
-    k_msm_keys_raw<<<blocks(i1 - i0, 256), 256, 0, s>>>(p, i0, i1, m->raw.p, scal, m->key.p, m->val.p,
-                                                        m->csort ? m->end_p : nullptr);
+    k_msm_keys_raw<<<blocks(i1 - i0, 256), 256, 0, s>>>(p, i0, i1, m->raw.p, scal, m->key.p, m->val.p);
   }
   int rc = msm_enqueue_tail(m, s);
   if (rc != FTZ_SUCCESS) return rc;

@@ -7,7 +7,7 @@
 
 #include "../dev/binv.h"
 #include "../dev/fp.h"
-#include "../dev/row29.h"
+#include "row29.h"
 
 using namespace fts;
 
@@ -153,7 +153,7 @@ extern "C" int ftz_binvcheck(int device, uint32_t n, const uint8_t* zmask, uint3
   return rc;
 }
 
-// ---- dev/row29.h against dev/fp29.h: every row of every wave multiplies,
+// ---- row29.h against dev/fp29.h: every row of every wave multiplies,
 // normalises and reduces its own operands (limbs normalised, or signed within
 // 2^29) row-wide, every lane the same one-lane, and lane r compares limb r.
 __device__ f29 rnd_f29(uint32_t& s, bool sgn) {

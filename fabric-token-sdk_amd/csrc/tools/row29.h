@@ -1,5 +1,5 @@
 // Row-distributed carry-free Fp arithmetic for latency-bound single-wave
-// chains (the MSM's Horner combination of the window sums): one field element
+// chains: one field element
 // per DPP row of 16 lanes, lane r holding limb r of the 9 x 29-bit signed
 // representation of dev/fp29.h (lanes 9..15 hold 0), so a wave carries four
 // independent elements, one per row.
@@ -12,14 +12,16 @@
 // results are the SAME integers with the same normalised limbs as f29_mul_c /
 // f29_norm / f29_reduce (normalisation is unique: limbs 0..7 in [0, 2^29), limb
 // 8 the signed rest), so code built on them keeps f29's bounds and bytes.
-// tools/fpcheck.hip checks every routine against its f29 counterpart on the
-// device (ftz_rowcheck).
+// fpcheck.hip, the one user, checks every routine against its f29 counterpart
+// on the device (ftz_rowcheck) and times the products (ftz_rowbench); a Horner
+// chain of the MSM's window sums on these rows was measured and not kept
+// (profiles/r06/msm_row.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "fp29.h"
+#include "../dev/fp29.h"
 
 namespace fts {
 

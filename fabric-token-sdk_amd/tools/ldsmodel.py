@@ -7,7 +7,7 @@ costs max over banks of the distinct dwords it addresses there.  Lanes are
 a region of R dwords per sextet, slots of S dwords.  The patterns are the
 x-power's cyclotomic squaring and product (pattern_list) and the Miller step's
 squaring, normalised fixed line and pair-2 line (miller_patterns).  Used to
-pick sq_region_dwords' stride (FTS_SQ_PAD):
+pick sq_region_dwords' stride (SQ_PAD_MOD32):
     python fabric-token-sdk_amd/tools/ldsmodel.py
 """
 # LDS bank-conflict model of the sextet operand exchange (MI355X_MICROARCH.md LDS table)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""dev/row29.h on one MI355X: the device check against dev/fp29.h
+"""csrc/tools/row29.h on one MI355X: the device check against dev/fp29.h
 (ftz_rowcheck) and the cycles per dependent Montgomery product of one wave,
 one-lane f29_mul_c (impl 0) against the row-wide row_mul (impl 1).
     python fabric-token-sdk_amd/tools/rowbench.py

@@ -173,8 +173,8 @@ def test_binv_tree_device_check():
 
 
 def test_row29_device_check():
-    """dev/row29.h (one field element per 16-lane DPP row: the MSM Horner
-    chain's arithmetic) against dev/fp29.h on the device: products, carry
+    """csrc/tools/row29.h (one field element per 16-lane DPP row: arithmetic
+    for latency-bound one-wave chains) against dev/fp29.h on the device: products, carry
     normalisation, reduction, zero tests and four products at once through
     row_level, for normalised and signed-limb operands (1024 waves x 16 rounds
     x 4 rows): every limb identical"""
