@@ -648,6 +648,55 @@ void nym_fill(const ftz_owner_sig* s, const uint32_t* idx, size_t m, const NymDe
   });
 }
 
+// ---------------------------------------------------------------- pseudonym signing (BN254)
+bool nymsign_nym_ok(const uint8_t nym[64]) {
+  uint32_t x[8], y[8], t[8], pm[8];
+  fts::be32_to_limbs(x, nym);
+  fts::be32_to_limbs(y, nym + 32);
+  for (int i = 0; i < 8; i++) pm[i] = fts::P_MOD[i];
+  if (!fts::sub8(t, x, pm) || !fts::sub8(t, y, pm)) return false;  // a coordinate >= p
+  uint32_t o = 0;
+  for (int i = 0; i < 8; i++) o |= x[i] | y[i];
+  if (o == 0) return false;
+  fts::g1a a;
+  a.x = fts::fe_from_int<fts::ModP>(x);
+  a.y = fts::fe_from_int<fts::ModP>(y);
+  a.inf = false;
+  return fts::g1_on_curve(a);
+}
+
+bool nymsign_scalar_ok(const uint8_t k[32], bool nonzero) {
+  uint32_t v[8], t[8], rm[8];
+  fts::be32_to_limbs(v, k);
+  for (int i = 0; i < 8; i++) rm[i] = fts::R_MOD[i];
+  uint32_t o = 0;
+  for (int i = 0; i < 8; i++) o |= v[i];
+  const bool below = fts::sub8(t, v, rm) != 0;
+  explicit_bzero(v, sizeof v);  // the value may be a user secret
+  explicit_bzero(t, sizeof t);
+  return below && (o != 0 || !nonzero);
+}
+
+void nymsign_fill_prefix(uint8_t* pre, const uint8_t nym[64], const std::vector<uint8_t>& ipk_hash, size_t msg_len) {
+  constexpr size_t PRE = fts::NymCurve<fts::fp>::PRE;
+  memset(pre, 0, fts::NYM_PRE_SLOT);
+  memcpy(pre, "sign", 4);
+  memcpy(pre + 4 + 64, nym, 64);
+  memcpy(pre + 4 + 128, ipk_hash.data(), ipk_hash.size() < 32 ? ipk_hash.size() : 32);
+  for (size_t q = 0; q < fts::NymCurve<fts::fp>::TAIL; q++) {
+    size_t hi = 32 + msg_len + q;
+    pre[PRE + q] = hi < ipk_hash.size() ? ipk_hash[hi] : 0;
+  }
+}
+
+void encode_nym_signature(const uint8_t raw[128], uint8_t out[136]) {
+  for (int k = 0; k < 4; k++) {
+    out[34 * k] = (uint8_t)(((k + 1) << 3) | 2);
+    out[34 * k + 1] = 0x20;
+    memcpy(out + 34 * k + 2, raw + 32 * k, 32);
+  }
+}
+
 }  // namespace ftsh
 
 namespace ftsh {

@@ -105,4 +105,20 @@ void nym_fill(const ftz_owner_sig* s, const uint32_t* idx, size_t m, const NymDe
               const std::function<void(size_t, const std::function<void(size_t)>&)>& par,
               int curve = FTZ_CURVE_FP256BN_AMCL);
 
+// ---- pseudonym signing on BN254 (dev/nymsign.h, ftz_sign_owner_signatures)
+// NymX || NymY as a signer hands it over: both coordinates canonical (< p),
+// not (0, 0) (gnark's infinity) and on the curve
+bool nymsign_nym_ok(const uint8_t nym[64]);
+// 32 bytes big-endian below the BN254 group order r; nonzero: also not 0
+bool nymsign_scalar_ok(const uint8_t k[32], bool nonzero);
+// the 176-byte transcript prefix slot of one signature: "sign", zeros where the
+// device writes t, Nym, copy(proofData[132:], ipk.Hash) and the 2 bytes that
+// follow a message of msg_len bytes (zero unless the hash is that long)
+void nymsign_fill_prefix(uint8_t* pre, const uint8_t nym[64], const std::vector<uint8_t>& ipk_hash, size_t msg_len);
+// proto(NymSignature{ProofC, ProofSSk, ProofSRNym, Nonce}) from the device's
+// four 32-byte integers: per field its tag (0x0A, 0x12, 0x1A, 0x22), the
+// length 0x20 and the 32 bytes, leading zeros kept (Zr.Bytes() is fixed-width).
+// Always FTZ_NYMSIG_LEN = 136 bytes.
+void encode_nym_signature(const uint8_t raw[128], uint8_t out[136]);
+
 }  // namespace ftsh

@@ -667,6 +667,49 @@ class Idemix:
         """GetOwnerVerifier(tok.Owner) (validator_transfer.go:66)"""
         return OwnerVerifier(self, owner)
 
+    def add_signer(self, sk):
+        """register a user secret (32 bytes big-endian, 1 <= sk < r; at most 8 per
+        handle; BN254 handles only) -> signer index"""
+        sk = bytes(sk)
+        if len(sk) != 32:
+            raise ValueError("the user secret is 32 bytes big-endian")
+        idx = ctypes.c_int32()
+        _check(self._lib.ftz_idemix_add_signer(self._h, sk, ctypes.byref(idx)), self._lib)
+        return idx.value
+
+    def sign_owner_signatures(self, items):
+        """items: (signer index, r_nym, nym (NymX || NymY), msg[, 32 entropy bytes or
+        None]) -> (NymSignature protos, FTZ codes).  A code other than FTZ_OK
+        (FTZ_ERR_OWNER: the nym is not a canonical finite point of the curve) comes
+        with 136 zero bytes.  SigningIdentity.Sign with the randomness drawn from an
+        HMAC-SHA-256 DRBG on the device; with entropy, hedged by it."""
+        items = list(items)
+        arr, keep = _abi.pack_nym_sign_items(items)
+        return self.sign_owner_signatures_packed(arr, len(items))
+
+    def sign_owner_signatures_packed(self, arr, n):
+        """pre-packed ftz_nym_sign_item array (bench: the binding's packing stays out of the timed call)"""
+        sigs = ctypes.create_string_buffer(max(n, 1) * _abi.FTZ_NYMSIG_LEN)
+        codes = (ctypes.c_int32 * max(n, 1))()
+        _check(self._lib.ftz_sign_owner_signatures(self._h, n, arr, sigs, codes), self._lib)
+        raw, L = sigs.raw, _abi.FTZ_NYMSIG_LEN
+        return [raw[i * L:(i + 1) * L] for i in range(n)], list(codes[:n])
+
+    def make_nyms(self, signer, r_nyms):
+        """MakeNym in batches: r_nyms (32 bytes big-endian each, < r) -> the
+        pseudonyms sk HSk + r_nym HRand as NymX || NymY (64 bytes each)"""
+        r_nyms = [bytes(r) for r in r_nyms]
+        if any(len(r) != 32 for r in r_nyms):
+            raise ValueError("r_nym is 32 bytes big-endian")
+        n = len(r_nyms)
+        out = ctypes.create_string_buffer(max(n, 1) * 64)
+        _check(self._lib.ftz_idemix_make_nyms(self._h, signer, n, b"".join(r_nyms), out), self._lib)
+        return [out.raw[i * 64:(i + 1) * 64] for i in range(n)]
+
+    def owner_signer(self, signer, r_nym, nym):
+        """the driver.Signer of a pseudonym (identity/msp/idemix/id.go:195-210)"""
+        return OwnerSigner(self, signer, r_nym, nym)
+
     def close(self):
         if self._h:
             self._lib.ftz_idemix_destroy(self._h)
@@ -691,6 +734,25 @@ class OwnerVerifier:
         code = self.ix.verify_owner_signatures([(self.owner, bytes(message), bytes(sigma))])[0]
         if code != FTZ_OK:
             raise ZKError(code)
+
+
+class OwnerSigner:
+    """driver.Signer of an idemix pseudonym (identity/msp/idemix/id.go:195-210
+    SigningIdentity.Sign): signer = an index from Idemix.add_signer, r_nym and
+    nym = the pseudonym's randomness and NymX || NymY (Idemix.make_nyms)."""
+
+    def __init__(self, ix, signer, r_nym, nym):
+        self.ix = ix
+        self.signer = signer
+        self.r_nym = bytes(r_nym)
+        self.nym = bytes(nym)
+
+    def sign(self, message, entropy=None):
+        """Signer.Sign(message): the NymSignature proto; raises ZKError on a refused nym"""
+        sigs, codes = self.ix.sign_owner_signatures([(self.signer, self.r_nym, self.nym, bytes(message), entropy)])
+        if codes[0] != FTZ_OK:
+            raise ZKError(codes[0])
+        return sigs[0]
 
 
 class Ecdsa:

@@ -87,6 +87,42 @@ def pack_owner_sigs(items):
     return arr, keep
 
 
+FTZ_IDEMIX_MAX_SIGNERS = 8
+FTZ_NYMSIG_LEN = 136
+
+
+class NymSignItem(ctypes.Structure):
+    _fields_ = [("msg", ctypes.c_void_p), ("msg_len", ctypes.c_size_t), ("signer", ctypes.c_int32),
+                ("r_nym", ctypes.c_void_p), ("nym", ctypes.c_void_p), ("entropy", ctypes.c_void_p)]
+
+
+def pack_nym_sign_items(items):
+    """items: (signer index, r_nym (32 bytes), nym (64 bytes), msg[, 32 entropy
+    bytes or None]); identical msg objects share one buffer.  Returns
+    (ftz_nym_sign_item array, keepalive)."""
+    items = list(items)
+    arr = (NymSignItem * max(len(items), 1))()
+    keep = []
+    bufs = {}
+
+    def buf(b):
+        k = id(b)
+        if k not in bufs:
+            bufs[k] = ctypes.create_string_buffer(bytes(b), max(len(b), 1))
+            keep.append((b, bufs[k]))
+        return ctypes.cast(bufs[k], ctypes.c_void_p)
+
+    for i, it in enumerate(items):
+        signer, r_nym, nym, m = it[0], it[1], it[2], it[3]
+        ent = it[4] if len(it) > 4 else None
+        if len(r_nym) != 32 or len(nym) != 64:
+            raise ValueError("r_nym is 32 bytes and nym 64 bytes")
+        if ent is not None and len(ent) != 32:
+            raise ValueError("entropy must be 32 bytes")
+        arr[i] = NymSignItem(buf(m), len(m), signer, buf(r_nym), buf(nym), buf(ent) if ent is not None else None)
+    return arr, keep
+
+
 FTZ_ERR_IDENTITY = 13
 MESSAGES[FTZ_ERR_IDENTITY] = "failed parsing received public key: the identity is not an ECDSA public key"
 
@@ -351,6 +387,7 @@ SYMBOLS = ["ftz_options_default", "ftz_ctx_create", "ftz_ctx_create_ex", "ftz_ct
            "ftz_batch_destroy", "ftz_batch_challenges", "ftz_msm_g1", "ftz_msm_load", "ftz_msm_load_gen", "ftz_msm_run", "ftz_msm_set_scalars", "ftz_msm_run_scalars", "ftz_host_alloc", "ftz_host_free", "ftz_msm_info", "ftz_msm_destroy", "ftz_g1_sum",
            "ftz_token_request_decode", "ftz_verify_token_requests", "ftz_verify_token_requests_batched", "ftz_ctx_request_stats",
            "ftz_idemix_create", "ftz_verify_owner_signatures", "ftz_idemix_set_strict_nym", "ftz_idemix_destroy", "ftz_audit_owners",
+           "ftz_idemix_add_signer", "ftz_sign_owner_signatures", "ftz_idemix_make_nyms",
            "ftz_ecdsa_create", "ftz_ecdsa_add_identity", "ftz_verify_ecdsa_signatures", "ftz_x509_public_key", "ftz_ecdsa_destroy",
            "ftz_ecdsa_add_signer", "ftz_sign_ecdsa",
            "ftz_prove_transfers", "ftz_prove_issues", "ftz_ctx_prover_stats", "ftz_prover_load_transfers", "ftz_prover_load_issues",
@@ -443,6 +480,10 @@ def load():
     lib.ftz_idemix_set_strict_nym.argtypes = [vp, ctypes.c_int]
     lib.ftz_idemix_destroy.argtypes = [vp]
     lib.ftz_idemix_destroy.restype = None
+    lib.ftz_idemix_add_signer.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(i32)]
+    lib.ftz_sign_owner_signatures.argtypes = [vp, sz, ctypes.POINTER(NymSignItem), ctypes.c_char_p,
+                                              ctypes.POINTER(i32)]
+    lib.ftz_idemix_make_nyms.argtypes = [vp, i32, sz, ctypes.c_char_p, ctypes.c_char_p]
     lib.ftz_ecdsa_create.argtypes = [vp, ctypes.POINTER(vp)]
     lib.ftz_ecdsa_add_identity.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(i32)]
     lib.ftz_verify_ecdsa_signatures.argtypes = [vp, sz, ctypes.POINTER(EcdsaSig), ctypes.POINTER(i32)]

@@ -425,6 +425,55 @@ typedef struct {
 } ftz_owner_audit;
 int ftz_audit_owners(ftz_idemix* ix, size_t n, const ftz_owner_audit* items, int32_t* codes);
 
+/* Signing on the same handle, BN254 only: the owner's signature of each input
+ * token of a transfer.  Replaces SigningIdentity.Sign
+ * (identity/msp/idemix/id.go:195-210 -> CSP.Sign(UserKey, msg,
+ * IdemixNymSignerOpts{Nym, IssuerPK}) -> IBM/idemix NewNymSignature) and, with
+ * ftz_idemix_make_nyms, the pseudonym derivation MakeNym
+ * (Nym = sk HSk + RNym HRand).  The reference draws r_sk, r_rnym and the nonce
+ * from crypto/rand; here they are the output of an HMAC-SHA-256 DRBG (the
+ * generator of RFC 6979, not that RFC's scheme: 512 bits reduced mod r per
+ * value, bias below 2^-250, no retry loop) keyed with the user secret,
+ * SHA-256(msg) and RNym, computed on the device and never copied to the host.
+ * With `entropy` = NULL a signature is a function of (sk, RNym, Nym, msg); with
+ * 32 bytes of fresh randomness the DRBG is seeded with
+ * SHA-256(SHA-256(msg) || entropy) in place of SHA-256(msg) (a hedged nonce: a
+ * repeated seed still cannot repeat the randomness across two messages).  So
+ * the bytes differ from the reference's while every signature passes
+ * NymSignature.Ver.  Up to 8 user secrets per handle, kept in device memory
+ * (zeroed when the handle is destroyed); the library wipes its own host copies
+ * of sk and RNym, the caller's buffers are the caller's to wipe.  Table
+ * addresses depend on the secret scalars: for a process that owns its device.
+ * The library does NOT check that `nym` belongs to (sk, RNym): a mismatched
+ * nym gives a well-formed signature that does not verify;
+ * ftz_idemix_make_nyms is how a caller derives matching nyms.  On an
+ * FP256BN_AMCL handle the three calls return FTZ_E_INVALID (the device has no
+ * scalar field for that curve).  Not wired into ftz_verify_token_requests. */
+#define FTZ_IDEMIX_MAX_SIGNERS 8
+#define FTZ_NYMSIG_LEN 136 /* proto(NymSignature): four fields of tag, length 0x20 and 32 bytes, always */
+typedef struct {
+  const uint8_t* msg;     /* hashed on the device                                            */
+  size_t msg_len;
+  int32_t signer;         /* index from ftz_idemix_add_signer                                */
+  const uint8_t* r_nym;   /* 32 bytes big-endian, < r: the pseudonym's RNym                   */
+  const uint8_t* nym;     /* 64 bytes: NymX || NymY as in SerializedIdemixIdentity            */
+  const uint8_t* entropy; /* NULL, or 32 bytes of fresh randomness                            */
+} ftz_nym_sign_item;
+/* sk: the user secret, 32 bytes big-endian, 1 <= sk < r (else FTZ_E_INVALID, as
+ * is a ninth signer). */
+int ftz_idemix_add_signer(ftz_idemix* ix, const uint8_t sk[32], int32_t* signer);
+/* sigs: n slots of FTZ_NYMSIG_LEN bytes.  codes[i] = FTZ_OK, or FTZ_ERR_OWNER
+ * when `nym` is not a canonical finite point of the curve (a coordinate >= p,
+ * (0, 0), or off the curve; checked on the host, the slot is zeroed, the other
+ * items are unaffected).  An out-of-range signer, an r_nym >= r, a NULL r_nym
+ * or nym, a NULL message with a non-zero length or a message over 512 MiB is
+ * FTZ_E_INVALID for the call; thread-safe (one call at a time on the handle,
+ * verification included). */
+int ftz_sign_owner_signatures(ftz_idemix* ix, size_t n, const ftz_nym_sign_item* it, uint8_t* sigs, int32_t* codes);
+/* nyms[i] = sk HSk + r_nyms[i] HRand as NymX || NymY (64 bytes; r_nyms: n x 32
+ * bytes big-endian, each < r, else FTZ_E_INVALID for the call). */
+int ftz_idemix_make_nyms(ftz_idemix* ix, int32_t signer, size_t n, const uint8_t* r_nyms, uint8_t* nyms);
+
 /* ---- x509 ECDSA P-256 signatures: the auditor's signature of a request
  * (crypto/validator/validator.go:134-145), each issue action's issuer
  * signature (validator.go:170-176) and fabtoken owners.  Replaces
