@@ -19,11 +19,20 @@
 //     every slot busy, callers accumulate for the next free slot anyway;
 //   * transfers and issues share batches (the planner emits the same jobs).
 //
-// Batches cycle through opt.slots reusable slots (pinned staging blob, device
-// buffers, streams, events): the dispatcher plans batch k+1 on the host pool
-// while batches k, k-1, ... run on the device; a completion thread waits for
-// the oldest batch in flight, scatters its verdict codes back to the requests
-// and recycles the slot.  A request returns when all its proofs are done.
+// Batches cycle through reusable buffer sets (pinned staging blob, device
+// buffers, events): the dispatcher plans batch k+1 on the host pool while
+// batches k, k-1, ... run on the device; a completion thread waits for the
+// oldest batch in flight, scatters its verdict codes back to the requests and
+// recycles the set.  A request returns when all its proofs are done.
+//
+// Buffer sets are apart from the context's stream triples (opt.slots of them,
+// at most four): a pass takes its triple when it is dispatched, and a full
+// pass may be planned, uploaded and enqueued behind the pass running on its
+// triple (opt.lookahead, host/engine_policy.h), so the triple's next kernels
+// are already in its streams when that pass ends.  In-stream order keeps the
+// two apart: everything a pass puts on st[1] and st[2] waits on an event of
+// its own st[0] chain, which follows the k_verdict of the pass ahead, and that
+// pass joined its st[1] and st[2] work before its transcript hashes.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -37,6 +46,7 @@
 #include <vector>
 
 #include "../../include/ftsamd.h"
+#include "host/engine_policy.h"
 #include "rt_internal.h"
 
 using Clock = std::chrono::steady_clock;
@@ -71,8 +81,16 @@ struct Engine {
   size_t pending = 0;        // proofs queued and not yet handed to a batch (under mu)
   bool disp_holding = false;  // the dispatcher is waiting out a window (under mu)
   bool tail_split_done = false;  // the queue's last pass was cut in two (under mu; reset by new requests)
-  std::vector<ftz_batch*> slots;
-  std::deque<ftz_batch*> free_slots, inflight;
+  std::vector<ftz_batch*> slots;               // buffer sets: pol.buffer_sets() of them
+  std::deque<ftz_batch*> free_slots, inflight;  // inflight: every enqueued pass, in dispatch order
+  EnginePolicy pol;                             // which triple a pass takes (under mu)
+  // Capacities {h_blob, d_blob, d_scr, h_res} every set is levelled to (under
+  // mu): when planning grows one set, the idle ones follow at once and the
+  // busy ones when they complete, so that each set has met its largest pass
+  // after the first few passes of a context (a warm-up), not only after as
+  // many passes as there are sets -- no allocation inside a later job.
+  size_t want[4] = {0, 0, 0, 0};
+  uint64_t partial_ahead = 0;  // partial passes enqueued behind a running one (ftz_ctx_debug_engine_sets)
   ftz_engine_stats st{};
   Clock::time_point first, last;
   bool stop = false;
@@ -83,7 +101,40 @@ struct Engine {
   void completer();
   void fail_parts(ftz_batch* b, int rc, const std::string& err, std::vector<Request*>& wake);
   void requeue_solo(ftz_batch* b);
+  bool note_caps(const ftz_batch* b);
+  void level(ftz_batch* b, std::unique_lock<std::mutex>& lk);
 };
+
+static bool below(const ftz_batch* b, const size_t w[4]) {
+  return b->h_blob.cap < w[0] || b->d_blob.cap < w[1] || b->d_scr.cap < w[2] || b->h_res.cap < w[3];
+}
+
+// Set b was planned (mu held): raise the common capacities to its own; true if any rose.
+bool Engine::note_caps(const ftz_batch* b) {
+  const size_t c[4] = {b->h_blob.cap, b->d_blob.cap, b->d_scr.cap, b->h_res.cap};
+  bool rose = false;
+  for (int k = 0; k < 4; k++)
+    if (c[k] > want[k]) {
+      want[k] = c[k];
+      rose = true;
+    }
+  return rose;
+}
+
+// Bring set b, which the calling thread owns (not free, not in flight), up to
+// the common capacities; mu is held on entry and exit and released around the
+// allocations.  Best effort: a set that cannot grow now grows, or fails with
+// FTZ_E_NOMEM, when a pass that needs the room is planned into it.
+void Engine::level(ftz_batch* b, std::unique_lock<std::mutex>& lk) {
+  while (below(b, want)) {
+    size_t w[4];
+    memcpy(w, want, sizeof(w));
+    lk.unlock();
+    int rc = slot_grow_to(b, w);
+    lk.lock();
+    if (rc != FTZ_SUCCESS) break;
+  }
+}
 
 static PlanItem item_of(const Request* r, size_t i) {
   PlanItem it;
@@ -186,7 +237,12 @@ void Engine::dispatcher() {
         continue;  // re-evaluate: a full batch, a completion, or the deadline
       }
     }
-    cv_free.wait(lk, [&]() { return !free_slots.empty(); });
+    // A buffer set, and a triple this pass may take: one with nothing on it,
+    // or, for a pass that will close at its item budget, one with room behind
+    // its running pass.  (A pass that closes early at its byte or pair budget
+    // is full too, but that shows only once it is cut: it is then placed by
+    // what it is, below, after waiting here like a partial one.)
+    cv_free.wait(lk, [&]() { return !free_slots.empty() && pol.pick(pending >= B) >= 0; });
     ftz_batch* b = free_slots.front();
     free_slots.pop_front();
     b->parts.clear();
@@ -232,6 +288,9 @@ void Engine::dispatcher() {
       if (r->next == r->n) q.pop_front();
       if (!room() || r->solo) break;
     }
+    // full: closed at the item, byte or pair budget of a whole batch (not a
+    // first pass, a tail half, a solo request's or the queue's remainder)
+    const bool full = Bp == B && (b->items.size() >= B || !room());
     lk.unlock();
     Clock::time_point t0 = Clock::now();
     int rc = slot_plan_items(b, b->items.size(), b->items.data());
@@ -241,21 +300,59 @@ void Engine::dispatcher() {
       // hand every request of the batch back and plan each on its own, so
       // that the error reaches only the request that caused it
       lk.lock();
+      (void)note_caps(b);
       requeue_solo(b);
       free_slots.push_back(b);
-      cv_free.notify_one();
       continue;
     }
-    if (rc == FTZ_SUCCESS) rc = slot_submit(b, true, true);
-    Clock::time_point t2 = Clock::now();
     std::string err = rc == FTZ_SUCCESS ? std::string() : g_err;
+    lk.lock();
+    if (note_caps(b)) {
+      // this pass grew its set: level the idle sets now (the dispatcher is the
+      // only taker of free sets, so they can leave the list and come back in
+      // their order), the busy ones as they complete
+      std::deque<ftz_batch*> idle;
+      idle.swap(free_slots);
+      for (ftz_batch* f : idle) level(f, lk);
+      for (auto it = idle.rbegin(); it != idle.rend(); ++it) free_slots.push_front(*it);
+    }
+    if (rc != FTZ_SUCCESS) {  // a planning error: nothing was enqueued and no triple taken
+      st.batches++;
+      st.proofs += b->items.size();
+      st.plan_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+      std::vector<Request*> wake;
+      fail_parts(b, rc, err, wake);
+      free_slots.push_back(b);
+      lk.unlock();
+      wake_all(wake);
+      lk.lock();
+      continue;
+    }
+    // The triple is chosen now, after planning: completions in the meantime
+    // only made room, and the pass goes behind the pass that ends soonest.
+    int t = pol.pick(full);
+    if (t < 0) {  // turned out partial (a solo request, a tail half) with every triple busy
+      cv_free.wait(lk, [&]() { return (t = pol.pick(full)) >= 0; });
+    }
+    const uint32_t ahead = pol.enqueue(t);
+    lk.unlock();
+    slot_set_triple(b, t);
+    Clock::time_point t1s = Clock::now();
+    rc = slot_submit(b, true, true);
+    Clock::time_point t2 = Clock::now();
+    if (rc != FTZ_SUCCESS) err = g_err;
     lk.lock();
     if (st.batches == 0 && inflight.empty()) first = t1;
     st.batches++;
     st.proofs += b->items.size();
     st.plan_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    st.submit_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    st.submit_ms += std::chrono::duration<double, std::milli>(t2 - t1s).count();
     st.max_in_flight = std::max<uint32_t>(st.max_in_flight, (uint32_t)inflight.size() + 1);
+    st.max_per_triple = std::max<uint32_t>(st.max_per_triple, ahead + 1);
+    if (ahead) {
+      st.queued_ahead++;
+      if (!full) partial_ahead++;
+    }
     if (rc != FTZ_SUCCESS) {
       if (b->pending) {  // enqueued part of the work before failing: let it drain first
         lk.unlock();
@@ -264,8 +361,8 @@ void Engine::dispatcher() {
       }
       std::vector<Request*> wake;
       fail_parts(b, rc, err, wake);
+      pol.release(b->triple);
       free_slots.push_back(b);
-      cv_free.notify_one();
       lk.unlock();
       wake_all(wake);
       lk.lock();
@@ -302,11 +399,21 @@ void Engine::completer() {
     last = Clock::now();
     st.wall_ms = std::chrono::duration<double, std::milli>(last - first).count();
     inflight.pop_front();
+    pol.release(b->triple);
     if (rc != FTZ_SUCCESS) {
       fail_parts(b, rc, err, wake);
     } else {
       for (auto& p : b->parts) finish_part(p.req, p.count, wake);
       b->parts.clear();
+    }
+    if (below(b, want)) {
+      // another set grew while this one ran: follow before it is used again;
+      // its triple is free meanwhile, and the callers need not wait for this
+      cv_free.notify_one();
+      lk.unlock();
+      wake_all(wake);
+      lk.lock();
+      level(b, lk);
     }
     free_slots.push_back(b);
     cv_free.notify_one();
@@ -323,7 +430,8 @@ static Engine* get_engine(ftz_ctx* c, int& rc) {
   if (c->eng) return c->eng;
   Engine* e = new Engine();
   e->ctx = c;
-  for (uint32_t k = 0; k < c->opt.slots; k++) {
+  e->pol = EnginePolicy((uint32_t)c->triples.size(), c->opt.slots, c->opt.lookahead);
+  for (uint32_t k = 0; k < e->pol.buffer_sets(); k++) {
     ftz_batch* b = new ftz_batch();
     b->ctx = c;
     rc = slot_init(b);
@@ -364,6 +472,8 @@ int engine_verify(ftz_ctx* c, size_t n, const ftz_transfer* tx, const ftz_issue*
     e->tail_split_done = false;
     // a dispatcher waiting out a window only needs waking for a full batch
     if (!e->disp_holding || e->pending >= e->ctx->opt.batch) e->cv_q.notify_one();
+    // ... or waiting for a triple: a batch that became full may queue behind a running pass
+    if (e->pending >= e->ctx->opt.batch) e->cv_free.notify_one();
   }
   {
     std::unique_lock<std::mutex> lk(r.m);
@@ -406,5 +516,26 @@ extern "C" int ftz_ctx_engine_stats(ftz_ctx* c, ftz_engine_stats* out, int reset
   std::lock_guard<std::mutex> lk2(e->mu);
   *out = e->st;
   if (reset) e->st = ftz_engine_stats{};
+  return FTZ_SUCCESS;
+}
+
+extern "C" int ftz_ctx_debug_engine_sets(ftz_ctx* c, uint64_t* caps, size_t max_sets, size_t* n_sets,
+                                         uint64_t* partial_ahead) {
+  if (!c) return set_err(FTZ_E_INVALID, "null context");
+  if (n_sets) *n_sets = 0;
+  if (partial_ahead) *partial_ahead = 0;
+  std::lock_guard<std::mutex> lk(c->eng_mu);
+  Engine* e = c->eng;
+  if (!e) return FTZ_SUCCESS;
+  std::lock_guard<std::mutex> lk2(e->mu);
+  if (n_sets) *n_sets = e->slots.size();
+  if (partial_ahead) *partial_ahead = e->partial_ahead;
+  for (size_t k = 0; caps && k < e->slots.size() && k < max_sets; k++) {
+    const ftz_batch* b = e->slots[k];
+    caps[4 * k] = b->h_blob.cap;
+    caps[4 * k + 1] = b->d_blob.cap;
+    caps[4 * k + 2] = b->d_scr.cap;
+    caps[4 * k + 3] = b->h_res.cap;
+  }
   return FTZ_SUCCESS;
 }

@@ -71,6 +71,16 @@ struct DevMem {
     if (e == hipSuccess) cap = want;
     return e;
   }
+  // exactly c bytes of capacity if it has fewer (the engine levels its buffer sets)
+  hipError_t grow_to(size_t c) {
+    if (c <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc(&p, c);
+    if (e == hipSuccess) cap = c;
+    return e;
+  }
 };
 struct PinnedMem {
   uint8_t* p = nullptr;
@@ -86,6 +96,15 @@ struct PinnedMem {
     size_t want = n + n / 4 + 4096;
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
     if (e == hipSuccess) cap = want;
+    return e;
+  }
+  hipError_t grow_to(size_t c) {
+    if (c <= cap) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipHostMalloc(&p, c, hipHostMallocDefault);
+    if (e == hipSuccess) cap = c;
     return e;
   }
 };
@@ -180,6 +199,7 @@ struct ftz_batch {
   hipEvent_t ev[20];
   bool ev_init = false;
   hipStream_t st[3] = {nullptr, nullptr, nullptr};
+  int triple = -1;  // index into ctx->triples of st (the engine moves its sets between triples)
   bool pending = false;
   uint64_t jobs_last[FTZ_NKERNELS] = {};
   ftz_stats stats{};
@@ -194,6 +214,9 @@ struct ftz_batch {
 struct ftz_prover : ftz_batch {};
 
 int slot_init(ftz_batch* b);                                      // streams + events (once)
+void slot_set_triple(ftz_batch* b, int triple);                   // an idle slot's streams: ctx->triples[triple]
+// level an idle slot's grow-only buffers with caps = {h_blob, d_blob, d_scr, h_res} bytes
+int slot_grow_to(ftz_batch* b, const size_t caps[4]);
 int slot_plan_items(ftz_batch* b, size_t n, const PlanItem* items);  // plan + flatten into pinned staging
 int slot_submit(ftz_batch* b, bool upload, bool fetch_codes);      // enqueue (optionally the H2D copy first)
 int slot_wait(ftz_batch* b);                                       // block, collect stats

@@ -57,6 +57,7 @@ extern "C" void ftz_options_default(ftz_options* o) {
   o->msm_glv = 1;
   o->prover_tables = 1;
   o->msm_graph = 0;
+  o->lookahead = 0;  // measured slower at 1: the device has no idle time to give (profiles/r09)
 }
 
 extern "C" int ftz_ctx_create(const uint8_t* pp, size_t pp_len, int device, ftz_ctx** out) {
@@ -80,6 +81,7 @@ extern "C" int ftz_ctx_create_ex(const uint8_t* pp, size_t pp_len, int device, c
     if (o.msm_glv > 1 || o.msm_precompute > 1 || o.prover_tables > 1 || o.msm_graph > 1)
       return set_err(FTZ_E_INVALID, "msm_glv / msm_precompute / prover_tables / msm_graph must be 0 or 1");
     if (o.request_threads > 1024) return set_err(FTZ_E_INVALID, "request_threads out of range (0..1024)");
+    if (o.lookahead > 4) return set_err(FTZ_E_INVALID, "lookahead out of range (0..4)");
     if (o.msm_radix_bits && o.msm_radix_bits != 8 && o.msm_radix_bits != 9)
       return set_err(FTZ_E_INVALID, "msm_radix_bits must be 0, 8 or 9");
   }
@@ -115,8 +117,8 @@ extern "C" int ftz_ctx_create_ex(const uint8_t* pp, size_t pp_len, int device, c
     return set_err(FTZ_E_DEVICE, "hipStreamCreate failed");
   }
   // at most 4 triples (13 streams with the context's own: fits 16 hardware
-  // queues); engine slots beyond that share them round-robin, i.e. are planned
-  // ahead and queue behind the batch 4 slots earlier
+  // queues); engine passes beyond that (slots > 4, ftz_options.lookahead) are
+  // planned ahead and queue behind a running pass on its triple
   for (uint32_t k = 0; k < std::min<uint32_t>(c->opt.slots, 4); k++) {
     std::array<hipStream_t, 3> t{};
     bool ok = hipStreamCreateWithPriority(&t[0], hipStreamNonBlocking, prio_hi) == hipSuccess &&
@@ -383,11 +385,26 @@ int slot_init(ftz_batch* b) {
   // line jobs high priority, side G1 jobs -- which fill the SIMDs the chain
   // leaves idle -- low)
   ftz_ctx* c = b->ctx;
-  const auto& t = c->triples[c->next_triple.fetch_add(1) % c->triples.size()];
-  for (int k = 0; k < 3; k++) b->st[k] = t[k];
+  slot_set_triple(b, (int)(c->next_triple.fetch_add(1) % c->triples.size()));
   for (int k = 0; k < 20; k++)
     HC(hipEventCreateWithFlags(&b->ev[k], k == 17 ? (hipEventBlockingSync | hipEventDisableTiming) : 0));
   b->ev_init = true;
+  return FTZ_SUCCESS;
+}
+
+// The engine's buffer sets take their triple per pass (host/engine_policy.h);
+// only for a slot with nothing pending.
+void slot_set_triple(ftz_batch* b, int triple) {
+  const auto& t = b->ctx->triples[(size_t)triple];
+  for (int k = 0; k < 3; k++) b->st[k] = t[k];
+  b->triple = triple;
+}
+
+int slot_grow_to(ftz_batch* b, const size_t caps[4]) {
+  HC(b->h_blob.grow_to(caps[0]));
+  HC(b->d_blob.grow_to(caps[1]));
+  HC(b->d_scr.grow_to(caps[2]));
+  HC(b->h_res.grow_to(caps[3]));
   return FTZ_SUCCESS;
 }
 

@@ -55,7 +55,8 @@ class Context:
         """fexp: "exact" (FTZ_FEXP_EXACT, gnark-crypto v0.6.0) or "fuentes";
         batch / slots / window_us / threads and any other ftz_options field by name
         (hold_inflight, small_pass, msm_window_bits, msm_slot_cap, msm_seg_slots,
-        msm_glv, msm_precompute): job-engine and MSM options."""
+        msm_glv, msm_precompute, first_pass, tail_split, lookahead): job-engine and
+        MSM options."""
         self._lib = _abi.load()
         self.device = int(device)
         h = ctypes.c_void_p()
@@ -152,6 +153,15 @@ class Context:
         st = _abi.EngineStats()
         _check(self._lib.ftz_ctx_engine_stats(self._h, ctypes.byref(st), 1 if reset else 0), self._lib)
         return {k: getattr(st, k) for k, _ in _abi.EngineStats._fields_}
+
+    def engine_sets(self):
+        """testing (ftz_ctx_debug_engine_sets): ([(h_blob, d_blob, d_scr, h_res)
+        capacity in bytes of every buffer set of the job engine], partial passes
+        ever enqueued behind a running one)"""
+        n, pa = ctypes.c_size_t(), ctypes.c_uint64()
+        caps = (ctypes.c_uint64 * (4 * 512))()
+        _check(self._lib.ftz_ctx_debug_engine_sets(self._h, caps, 512, ctypes.byref(n), ctypes.byref(pa)), self._lib)
+        return [tuple(caps[4 * k:4 * k + 4]) for k in range(min(n.value, 512))], pa.value
 
     def prover_stats(self, reset=False):
         """host-side time of ftz_prove_* (ftz_ctx_prover_stats): wait / copy / plan / submit"""

@@ -203,7 +203,7 @@ class Options(ctypes.Structure):
                 ("msm_precompute", ctypes.c_uint32), ("prover_tables", ctypes.c_uint32),
                 ("msm_radix_bits", ctypes.c_uint32), ("first_pass", ctypes.c_uint32),
                 ("tail_split", ctypes.c_uint32), ("msm_graph", ctypes.c_uint32),
-                ("request_threads", ctypes.c_uint32)]
+                ("request_threads", ctypes.c_uint32), ("lookahead", ctypes.c_uint32)]
 
 
 HOLD_NEVER = 0xFFFFFFFF
@@ -301,7 +301,8 @@ class ProverHostStats(ctypes.Structure):
 class EngineStats(ctypes.Structure):
     _fields_ = [("batches", ctypes.c_uint64), ("proofs", ctypes.c_uint64), ("plan_ms", ctypes.c_double),
                 ("submit_ms", ctypes.c_double), ("device_ms", ctypes.c_double), ("wall_ms", ctypes.c_double),
-                ("max_in_flight", ctypes.c_uint32)]
+                ("max_in_flight", ctypes.c_uint32), ("queued_ahead", ctypes.c_uint32),
+                ("max_per_triple", ctypes.c_uint32)]
 
 
 class Transfer(ctypes.Structure):
@@ -380,7 +381,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "lib
 
 # every symbol include/ftsamd.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["ftz_options_default", "ftz_ctx_create", "ftz_ctx_create_ex", "ftz_ctx_destroy", "ftz_last_error",
-           "ftz_ctx_set_threads", "ftz_ctx_set_serial", "ftz_ctx_debug_poison", "ftz_ctx_set_debug", "ftz_ctx_set_layout", "ftz_ctx_info", "ftz_ctx_options", "ftz_ctx_engine_stats", "ftz_pp_validate", "ftz_pp_setup",
+           "ftz_ctx_set_threads", "ftz_ctx_set_serial", "ftz_ctx_debug_poison", "ftz_ctx_set_debug", "ftz_ctx_set_layout", "ftz_ctx_info", "ftz_ctx_options", "ftz_ctx_engine_stats", "ftz_ctx_debug_engine_sets", "ftz_pp_validate", "ftz_pp_setup",
            "ftz_commit_tokens", "ftz_audit_openings",
            "ftz_verify_transfers", "ftz_verify_issues", "ftz_batch_load_transfers", "ftz_batch_load_issues",
            "ftz_batch_run", "ftz_batch_submit", "ftz_batch_wait", "ftz_batch_codes", "ftz_batch_bitmap", "ftz_batch_stats", "ftz_batch_size",
@@ -439,6 +440,8 @@ def load():
     lib.ftz_audit_openings.argtypes = [vp, sz, ctypes.c_char_p, ctypes.POINTER(TokenOpening),
                                        ctypes.POINTER(ctypes.c_int32)]
     lib.ftz_ctx_engine_stats.argtypes = [vp, ctypes.POINTER(EngineStats), ctypes.c_int]
+    lib.ftz_ctx_debug_engine_sets.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(sz),
+                                              ctypes.POINTER(ctypes.c_uint64)]
     lib.ftz_ctx_prover_stats.argtypes = [vp, ctypes.POINTER(ProverHostStats), ctypes.c_int]
     lib.ftz_ctx_destroy.argtypes = [vp]
     lib.ftz_ctx_destroy.restype = None

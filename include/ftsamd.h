@@ -96,8 +96,13 @@ typedef struct {
   uint32_t struct_size; /* sizeof(ftz_options)                                          */
   uint32_t batch;       /* max proofs per device batch (default 8192: 4096 leaves the
                            pairing kernels at 1.6 sextet waves per SIMD, profiles/r02g_*) */
-  uint32_t slots;       /* batch slots of the job engine = batches in flight (default 4;
-                           measured best of 4/5/6/8, profiles/r02_slots_sweep.txt)      */
+  uint32_t slots;       /* passes the job engine runs side by side, each on a stream triple
+                           of its own (default 4; DESIGN section 2: 1 / 2 / 3 / 4 / 5
+                           batches in flight gave 400k / 444k / 500k / 538k / 542k
+                           transfers/s).  The context has min(slots, 4) triples; slots
+                           beyond 4 share them (and count as the next multiple of 4).
+                           The engine owns one buffer set per slot, and `lookahead`
+                           more per triple                                          */
   uint32_t window_us;   /* micro-batching: how long a partial batch may wait for more
                            callers while the GPU is busy (default 1000; seam sweep,
                            profiles/r03k/seamsweep.jsonl)                                */
@@ -145,6 +150,17 @@ typedef struct {
   uint32_t request_threads; /* threads decoding token requests (ftz_verify_token_requests*;
                            0 = threads): they share the host's cores with the planning
                            threads that feed the device                                  */
+  uint32_t lookahead;   /* full passes (closed at the item or pair budget: a big call)
+                           that may be planned, uploaded and enqueued behind a running
+                           pass on its stream triple, so that the next pass's first kernel
+                           starts the moment the running one ends and the host's plan and
+                           enqueue time leave the device's critical path.  Costs one more
+                           buffer set per triple and unit.  A partial
+                           pass (small callers) still needs an idle triple.  Default 0
+                           = off: at 1 the headline job was 3.3 % slower (0 of 5
+                           pairs) -- the device is busy 99.9 % of that job already, and
+                           a fourth concurrent pass only stretches the other three
+                           (profiles/r09/ab_lookahead.txt, trace_gaps.txt)          */
 } ftz_options;
 #define FTZ_HOLD_NEVER 0xFFFFFFFFu
 void ftz_options_default(ftz_options* opt);
@@ -229,9 +245,18 @@ typedef struct {
   double submit_ms;  /* sum over batches */
   double device_ms;  /* sum over batches, upload -> verdicts downloaded */
   double wall_ms;    /* first submission -> last completion */
-  uint32_t max_in_flight;
+  uint32_t max_in_flight;  /* passes enqueued at once, running or queued behind one */
+  uint32_t queued_ahead;   /* passes enqueued behind a running pass (ftz_options.lookahead) */
+  uint32_t max_per_triple; /* most passes enqueued on one stream triple at once */
 } ftz_engine_stats;
 int ftz_ctx_engine_stats(ftz_ctx* ctx, ftz_engine_stats* out, int reset);
+/* testing: the job engine's buffer sets.  caps receives, for each of at most
+ * max_sets sets, the capacities in bytes of its pinned staging blob, device
+ * blob, device scratch and pinned result buffer (4 values per set); *n_sets
+ * the number of sets the engine owns (0 before the first ftz_verify_* call);
+ * *partial_ahead how many partial passes were ever enqueued behind a running
+ * one (the engine's rule keeps it 0 while slots <= 4).  Any pointer may be NULL. */
+int ftz_ctx_debug_engine_sets(ftz_ctx* ctx, uint64_t* caps, size_t max_sets, size_t* n_sets, uint64_t* partial_ahead);
 
 /* Host-side time of ftz_prove_transfers / ftz_prove_issues since context
  * creation (or the last reset), summed over device passes: waiting for a pass
