@@ -183,12 +183,14 @@ struct CopyJob {
   uint32_t to_out;
 };
 
-enum CheckKind : uint8_t { CK_STATIC = 0, CK_PTS = 1, CK_HASH = 2 };
+// CK_GT (Pointcheval-Sanders passes only, job_verdict_gt): the pairing product
+// of pair job a is one in GT (the unity kernels' byte, k_fexp_hard_one)
+enum CheckKind : uint8_t { CK_STATIC = 0, CK_PTS = 1, CK_HASH = 2, CK_GT = 3 };
 struct Check {
   uint8_t kind;
   uint8_t code;  // error class reported if this check fails
   uint16_t pad;
-  uint32_t a, b;  // CK_PTS: pts range [a, a+b); CK_HASH: hash job a
+  uint32_t a, b;  // CK_PTS: pts range [a, a+b); CK_HASH: hash job a; CK_GT: pair job a
 };
 struct TxChecks {
   uint32_t wf_start, wf_count;  // first part ("well-formedness" / issue WF)
@@ -198,6 +200,7 @@ struct TxChecks {
 
 // error classes (mirror include/ftsamd.h)
 enum : int32_t { E_OK = 0, E_PARSE = 1, E_MALFORMED = 2, E_WF = 3, E_RANGE = 4, E_MEMBERSHIP = 5, E_PANIC = 6 };
+static constexpr int32_t E_PS_SIGNATURE = 14;  // FTZ_ERR_PS_SIGNATURE
 
 // ------------------------------------------------------------------ helpers
 FTS_HD g1a g1_load(const G1Dev& d) {
@@ -984,6 +987,24 @@ FTS_HD int32_t job_verdict(const TxChecks& t, const Check* ck, const uint8_t* pt
   return wf != E_OK ? wf : rg;
 }
 
+// The verdict of an item of a Pointcheval-Sanders pass (host/planner_ps.cpp):
+// its checks in order -- CK_PTS (R, S decode) then CK_GT, the unity byte of its
+// pair job -- in the WF part alone; the first failing one gives the code.
+FTS_HD int32_t job_verdict_gt(const TxChecks& t, const Check* ck, const uint8_t* pt_ok, const uint8_t* gt_ok) {
+  for (uint32_t k = 0; k < t.wf_count; k++) {
+    const Check& c = ck[t.wf_start + k];
+    bool fail = true;  // CK_STATIC, and kinds a PS pass does not plan
+    if (c.kind == CK_PTS) {
+      fail = false;
+      for (uint32_t q = 0; q < c.b; q++) fail = fail || !pt_ok[c.a + q];
+    } else if (c.kind == CK_GT) {
+      fail = !gt_ok[c.a];
+    }
+    if (fail) return c.code;
+  }
+  return E_OK;
+}
+
 }  // namespace fts
 
 // ------------------------------------------------------------------ sextet jobs
@@ -996,6 +1017,18 @@ FTS_HD int32_t job_verdict(const TxChecks& t, const Check* ck, const uint8_t* pt
 namespace fts {
 
 FTS_HD int sx_f12_index(int k) { return (k & 1) ? 3 + (k >> 1) : (k >> 1); }
+
+// Unity test of a GT value in the sextet layout.  Lane k holds coefficient k
+// in the canonical Montgomery form (q2_to_fp2: value < p, one representative),
+// so the value is one iff the lane of the constant term (F12 word 0) holds
+// (one, 0) and the five others (0, 0): sx_gt_lane_one is the lane's vote, and
+// sx_gt_votes_one reads the six votes of sextet sx (lanes 6 sx .. 6 sx + 5 of
+// the wave) out of the wave's 64-bit ballot.
+FTS_HD bool sx_gt_lane_one(int k, const fp2& a) {
+  const bool c0 = sx_f12_index(k) == 0 ? fe_eq(a.c0, fe_one<ModP>()) : fe_is_zero(a.c0);
+  return c0 && fe_is_zero(a.c1);
+}
+FTS_HD bool sx_gt_votes_one(uint64_t ballot, uint32_t sx) { return ((ballot >> (6 * sx)) & 63u) == 63u; }
 
 // Miller-loop lines of Q in consumption order (precompute_lines), each
 // evaluated at P, stored at lines[n * njobs + idx].  A pair with an infinity

@@ -1295,7 +1295,7 @@ void relocate_into(const Plan& b, const PieceBase& o, bool p2_g1out, bool keep_c
     j.p2 += p2_g1out ? o_g1 : o_pts;
     j.q2 = rel(j.q2, o_g2);
     j.p3 = rel(j.p3, o_g1);
-    j.bytes += o_arena;
+    j.bytes = rel(j.bytes, o_arena);
     *pr++ = j;
   }
   Seg* sg = reinterpret_cast<Seg*>(dst[PS_SEG]) + o.sec[PS_SEG];
@@ -1322,6 +1322,7 @@ void relocate_into(const Plan& b, const PieceBase& o, bool p2_g1out, bool keep_c
   for (Check c : b.ck) {
     if (c.kind == CK_PTS) c.a += o_pts;
     if (c.kind == CK_HASH) c.a += o_hmain;
+    if (c.kind == CK_GT) c.a += (uint32_t)o.sec[PS_PR];
     *ck++ = c;
   }
   TxChecks* tx = reinterpret_cast<TxChecks*>(dst[PS_TX]) + o.sec[PS_TX];

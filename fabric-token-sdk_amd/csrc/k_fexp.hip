@@ -93,3 +93,31 @@ __global__ void __launch_bounds__(64, 1) k_fexp_fc_hard(const PairJob* jobs, uin
   fp2 g = sq_fc_hard(x, pk);
   if (valid) sx_gt_bytes(arena + jobs[jc].bytes, x.k, g);
 }
+
+// The unity test of a Pointcheval-Sanders pass: k_fexp_hard / k_fexp_fc_hard up
+// to the lane's coefficient g, then "is the GT value one?" instead of its
+// bytes -- one byte per pair job in gt_ok.  Lane k votes on its coefficient
+// (sx_gt_lane_one) and the wave's ballot carries the six votes of sextet sx in
+// bits 6 sx .. 6 sx + 5.  Every lane of the wave reaches the ballot: the ghost
+// lanes 60..63 and the sextets past n vote with a neutral `true`, and nothing
+// returns before it.  Lane 0 of a sextet stores the job's byte.
+//
+// Fuentes-Castaneda: the kernel holds one^d for the exact result `one` and d =
+// 2 x (6 x^2 + 3 x + 1).  The exact result has order dividing r (it is an r-th
+// root of unity: (p^12 - 1) / r was applied), r is an odd prime, x < 2^63 < r
+// gives 0 < 6 x^2 + 3 x + 1 < r and 0 < 2 x < r, so gcd(d, r) = 1 and v -> v^d
+// is a bijection of the r-th roots of unity fixing one: one^d = 1 iff one = 1.
+__global__ void __launch_bounds__(64, 1) k_fexp_hard_one(uint32_t n, uint8_t* gt_ok, int32_t* park) {
+  SQ_KERNEL_PROLOGUE(n, SX_SLOTS_FEXP)
+  FEXP_PARK
+  const fp2 g = sq_fexp_hard_exact(x, pk);
+  const uint64_t votes = __ballot(!valid || sx_gt_lane_one(x.k, g));
+  if (valid && x.k == 0) gt_ok[job_] = sx_gt_votes_one(votes, sx_) ? 1 : 0;
+}
+__global__ void __launch_bounds__(64, 1) k_fexp_fc_hard_one(uint32_t n, uint8_t* gt_ok, int32_t* park) {
+  SQ_KERNEL_PROLOGUE(n, SX_SLOTS_FEXP)
+  FEXP_PARK
+  const fp2 g = sq_fc_hard(x, pk);
+  const uint64_t votes = __ballot(!valid || sx_gt_lane_one(x.k, g));
+  if (valid && x.k == 0) gt_ok[job_] = sx_gt_votes_one(votes, sx_) ? 1 : 0;
+}

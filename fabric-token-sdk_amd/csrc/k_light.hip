@@ -45,6 +45,16 @@ __global__ void __launch_bounds__(256) k_verdict(const TxChecks* tx, uint32_t n,
   if (c == E_OK) atomicOr(&bitmap[i >> 5], 1u << (i & 31));
 }
 
+// the verdicts of a Pointcheval-Sanders pass (CK_GT: the unity bytes of k_fexp_hard_one)
+__global__ void __launch_bounds__(256) k_verdict_gt(const TxChecks* tx, uint32_t n, const Check* ck,
+                                                    const uint8_t* pt_ok, const uint8_t* gt_ok, int32_t* codes,
+                                                    uint32_t* bitmap) {
+  JOB_KERNEL_PROLOGUE(n);
+  int32_t c = job_verdict_gt(tx[i], ck, pt_ok, gt_ok);
+  codes[i] = c;
+  if (c == E_OK) atomicOr(&bitmap[i >> 5], 1u << (i & 31));
+}
+
 // ---- prover
 __global__ void __launch_bounds__(128) k_rand(const RandJob* jobs, uint32_t n, const uint8_t* arena,
                                               uint32_t (*scal)[8]) {

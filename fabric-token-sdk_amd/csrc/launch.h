@@ -58,6 +58,8 @@ __global__ void k_hash(const HashJob* jobs, uint32_t n, const Seg* segs, const u
                        const uint8_t* canon, uint8_t* ok);
 __global__ void k_verdict(const TxChecks* tx, uint32_t n, const Check* ck, const uint8_t* pt_ok,
                           const uint8_t* hash_ok, int32_t* codes, uint32_t* bitmap);
+__global__ void k_verdict_gt(const TxChecks* tx, uint32_t n, const Check* ck, const uint8_t* pt_ok,
+                             const uint8_t* gt_ok, int32_t* codes, uint32_t* bitmap);
 __global__ void k_pp_decode(const uint8_t* raw, const uint32_t* g1off, uint32_t n1, const uint32_t* g2off,
                             uint32_t n2, G1Dev* g1, G2Dev* g2, uint8_t* g1bytes, uint8_t* g2bytes, uint8_t* ok);
 __global__ void k_g1_part(const G1Job* jobs, uint32_t n, const uint32_t* flist, uint32_t nfl, const uint32_t* vlist,
@@ -100,13 +102,18 @@ __global__ void k_fexp_hard(const PairJob* jobs, uint32_t n, uint8_t* arena, int
 __global__ void k_fexp_fc_mid1(uint32_t n, int32_t* park);
 __global__ void k_fexp_fc_mid2(uint32_t n, int32_t* park);
 __global__ void k_fexp_fc_hard(const PairJob* jobs, uint32_t n, uint8_t* arena, int32_t* park);
+// the last phase of a Pointcheval-Sanders pass: gt_ok[job] = (the GT value is one)
+__global__ void k_fexp_hard_one(uint32_t n, uint8_t* gt_ok, int32_t* park);
+__global__ void k_fexp_fc_hard_one(uint32_t n, uint8_t* gt_ok, int32_t* park);
 inline size_t fexp_park_bytes(size_t n_pr) {
   return ((n_pr + SX_JOBS_PER_WAVE - 1) / SX_JOBS_PER_WAVE) * 64 * (size_t)FEXP_PARK_SLOTS * 18 * sizeof(int32_t);
 }
 // exact (FTZ_FEXP_EXACT): easy part, three x-powers, hard part; Fuentes-Castaneda
-// (FTZ_FEXP_FUENTES): easy part and x-powers with its two glue steps
+// (FTZ_FEXP_FUENTES): easy part and x-powers with its two glue steps.  With
+// gt_ok (Pointcheval-Sanders passes) the last phase is the unity test instead
+// of the GT bytes.
 inline void launch_fexp(bool exact, const PairJob* jobs, uint32_t n, const F12Dev* fbuf, uint8_t* arena,
-                        int32_t* park, hipStream_t s) {
+                        int32_t* park, hipStream_t s, uint8_t* gt_ok = nullptr) {
   if (!n) return;
   const uint32_t nb = (n + SX_JOBS_PER_WAVE - 1) / SX_JOBS_PER_WAVE;
   k_fexp_easy_a<<<nb, 64, 0, s>>>(n, fbuf, park);
@@ -114,7 +121,10 @@ inline void launch_fexp(bool exact, const PairJob* jobs, uint32_t n, const F12De
   k_fexp_easy_b<<<nb, 64, 0, s>>>(n, fbuf, park);
   if (exact) {
     for (int e = 0; e < 3; e++) k_fexp_expt<<<nb, 64, 0, s>>>(n, park, e, e + 1, 4);
-    k_fexp_hard<<<nb, 64, 0, s>>>(jobs, n, arena, park);
+    if (gt_ok)
+      k_fexp_hard_one<<<nb, 64, 0, s>>>(n, gt_ok, park);
+    else
+      k_fexp_hard<<<nb, 64, 0, s>>>(jobs, n, arena, park);
     return;
   }
   k_fexp_expt<<<nb, 64, 0, s>>>(n, park, 0, 1, FC_EXPT_SLOT);
@@ -122,7 +132,10 @@ inline void launch_fexp(bool exact, const PairJob* jobs, uint32_t n, const F12De
   k_fexp_expt<<<nb, 64, 0, s>>>(n, park, 3, 4, FC_EXPT_SLOT);
   k_fexp_fc_mid2<<<nb, 64, 0, s>>>(n, park);
   k_fexp_expt<<<nb, 64, 0, s>>>(n, park, 5, 6, FC_EXPT_SLOT);
-  k_fexp_fc_hard<<<nb, 64, 0, s>>>(jobs, n, arena, park);
+  if (gt_ok)
+    k_fexp_fc_hard_one<<<nb, 64, 0, s>>>(n, gt_ok, park);
+  else
+    k_fexp_fc_hard<<<nb, 64, 0, s>>>(jobs, n, arena, park);
 }
 
 // prover (k_light.hip)

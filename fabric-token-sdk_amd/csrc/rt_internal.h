@@ -18,6 +18,7 @@
 #include "dev/jobs.h"
 #include "dev/sx29.h"
 #include "host/planner.h"
+#include "host/planner_ps.h"
 
 using namespace fts;
 using namespace ftsh;
@@ -174,6 +175,11 @@ struct ftz_ctx {
   // slot behind ftz_commit_tokens / ftz_audit_openings
   std::mutex aux_mu;
   struct ftz_batch* aux = nullptr;
+  // slot behind ftz_verify_ps_signatures / ftz_pp_audit_signed_values: buffers,
+  // events and planning state of its own, so a call neither waits for nor
+  // touches the engine's passes (it shares the context's stream triples only)
+  std::mutex ps_mu;
+  struct ftz_batch* ps = nullptr;
 };
 
 // ------------------------------------------------------------------ batch slots
@@ -181,7 +187,7 @@ struct ftz_ctx {
 // one grow-only buffer.
 struct ScratchLayout {
   size_t pts, pt_ok, scal, canon, g1out, pnorm, g2out, fbuf, fxpark, lines2, part1, part1p, part2, vtab1, vtab1p, hash_ok, hash_ok_pre,
-      codes, bitmap, total;
+      codes, bitmap, gt_ok, total;
 };
 
 // One batch: its planning state, pinned staging blob, device blob + scratch,
@@ -190,6 +196,7 @@ struct ScratchLayout {
 struct ftz_batch {
   ftz_ctx* ctx = nullptr;
   bool prover = false;
+  bool ps = false;  // a Pointcheval-Sanders pass: the unity test and k_verdict_gt in place of the GT bytes and k_verdict
   size_t n = 0;
   PlanWork work;
   FlatPlan fp;
@@ -218,6 +225,7 @@ void slot_set_triple(ftz_batch* b, int triple);                   // an idle slo
 // level an idle slot's grow-only buffers with caps = {h_blob, d_blob, d_scr, h_res} bytes
 int slot_grow_to(ftz_batch* b, const size_t caps[4]);
 int slot_plan_items(ftz_batch* b, size_t n, const PlanItem* items);  // plan + flatten into pinned staging
+int slot_plan_ps(ftz_batch* b, size_t n, const PsIn* items);          // the same for a Pointcheval-Sanders pass
 int slot_submit(ftz_batch* b, bool upload, bool fetch_codes);      // enqueue (optionally the H2D copy first)
 int slot_wait(ftz_batch* b);                                       // block, collect stats
 void slot_free(ftz_batch* b);                                      // sync + release everything

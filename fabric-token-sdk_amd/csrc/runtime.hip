@@ -293,6 +293,11 @@ extern "C" void ftz_ctx_destroy(ftz_ctx* c) {
     delete c->aux;
     c->aux = nullptr;
   }
+  if (c->ps) {
+    slot_free(c->ps);
+    delete c->ps;
+    c->ps = nullptr;
+  }
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (auto& t : c->triples)
     for (hipStream_t x : t)
@@ -448,6 +453,7 @@ static void scratch_layout(ftz_batch* b) {
   s.hash_ok_pre = take(f.cnt[PS_HPRE]);
   s.codes = take(sizeof(int32_t) * b->n);
   s.bitmap = take(sizeof(uint32_t) * ((b->n + 31) / 32 + 1));
+  s.gt_ok = take(b->ps ? n_pr : 0);
   s.total = o;
 }
 
@@ -483,6 +489,12 @@ int slot_plan_items(ftz_batch* b, size_t n, const PlanItem* items) {
       if ((items[i].kind == 0 && items[i].t.proof == poison) || (items[i].kind == 1 && items[i].i.proof == poison))
         return set_err(FTZ_E_INVALID, "poisoned item (ftz_ctx_debug_poison)");
   plan_items(b->ctx->pp, n, items, b->work, *b->ctx->pool);
+  return slot_finish_plan(b, n, false);
+}
+
+int slot_plan_ps(ftz_batch* b, size_t n, const PsIn* items) {
+  b->ps = true;
+  plan_ps_items(n, items, b->work, *b->ctx->pool);
   return slot_finish_plan(b, n, false);
 }
 
@@ -594,7 +606,7 @@ struct SlotPtrs {
   const B64Job* b64;
   const CopyJob *cp, *cp2;
   G1Dev* pts;
-  uint8_t *pt_ok, *canon, *hash_ok, *hash_ok_pre;
+  uint8_t *pt_ok, *canon, *hash_ok, *hash_ok_pre, *gt_ok;
   uint32_t (*scal)[8];
   G1Dev* g1out;
   G1Dev* pnorm;
@@ -664,6 +676,7 @@ static SlotPtrs slot_ptrs(ftz_batch* b) {
   p.hash_ok_pre = s + l.hash_ok_pre;
   p.codes = reinterpret_cast<int32_t*>(s + l.codes);
   p.bitmap = reinterpret_cast<uint32_t*>(s + l.bitmap);
+  p.gt_ok = s + l.gt_ok;
   p.n_dec = (uint32_t)f.cnt[PS_DEC];
   p.n_zr = (uint32_t)f.cnt[PS_ZR];
   p.n_sc = (uint32_t)f.cnt[PS_SC];
@@ -743,8 +756,9 @@ static void launch_miller(ftz_ctx* c, const SlotPtrs& p, hipStream_t s) {
                                                                  p.fbuf);
 }
 
-static void launch_fexp(ftz_ctx* c, const SlotPtrs& p, hipStream_t s) {
-  launch_fexp(c->opt.fexp != FTZ_FEXP_FUENTES, p.pr, p.n_pr, p.fbuf, p.arena, p.fxpark, s);
+static void launch_fexp(ftz_ctx* c, const SlotPtrs& p, hipStream_t s, bool unity = false) {
+  launch_fexp(c->opt.fexp != FTZ_FEXP_FUENTES, p.pr, p.n_pr, p.fbuf, p.arena, p.fxpark, s,
+              unity ? p.gt_ok : nullptr);
 }
 
 // Verification pipeline.  Three streams after the light decode/scalar kernels:
@@ -805,14 +819,16 @@ int slot_submit(ftz_batch* b, bool upload, bool fetch_codes) {
   if (p.n_pr)
     launch_miller(c, p, s);
   HC(hipEventRecord(e[7], s));
-  launch_fexp(c, p, s);
+  launch_fexp(c, p, s, b->ps);
   HC(hipEventRecord(e[8], s));
   HC(hipStreamWaitEvent(s, e[12], 0));
   HC(hipEventRecord(e[9], s));
   if (p.n_hm)
     k_hash<<<blocks_for(p.n_hm, 128), 128, 0, s>>>(p.hmain, p.n_hm, p.seg, p.arena, p.scal, p.canon, p.hash_ok);
   HC(hipEventRecord(e[10], s));
-  if (p.n_tx)
+  if (p.n_tx && b->ps)
+    k_verdict_gt<<<blocks_for(p.n_tx, 256), 256, 0, s>>>(p.tx, p.n_tx, p.ck, p.pt_ok, p.gt_ok, p.codes, p.bitmap);
+  else if (p.n_tx)
     k_verdict<<<blocks_for(p.n_tx, 256), 256, 0, s>>>(p.tx, p.n_tx, p.ck, p.pt_ok, p.hash_ok, p.codes, p.bitmap);
   HC(hipEventRecord(e[13], s));
   if (fetch_codes && b->n) HC(hipMemcpyAsync(b->h_res.p, p.codes, b->n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1048,7 +1064,7 @@ int prover_submit(ftz_batch* b, bool upload, bool fetch) {
   else if (p.n_pr)
     launch_miller(c, p, s);
   HC(hipEventRecord(e[7], s));
-  launch_fexp(c, p, s);
+  launch_fexp(c, p, s, b->ps);
   HC(hipEventRecord(e[8], s));
   HC(hipStreamWaitEvent(s, e[12], 0));
   HC(hipEventRecord(e[9], s));
@@ -1382,4 +1398,77 @@ extern "C" int ftz_audit_openings(ftz_ctx* c, size_t n, const uint8_t* commitmen
                                   int32_t* codes) {
   if (n && (!commitments || !codes)) return set_err(FTZ_E_INVALID, "null argument");
   return openings_run(c, n, t, commitments, nullptr, codes);
+}
+
+// ------------------------------------------------------------------ Pointcheval-Sanders signatures
+// pssign.SignVerifier.Verify (sign.go:125-160) in passes of at most 4 x batch
+// items (the engine's pair budget) on the context's PS slot: decode R, S; m, h;
+// P1 = -S; t' = PK0 + m PK1 + h PK2 with the pair-2 lines; Miller loops; the
+// final exponentiation ending in the unity test; k_verdict_gt.
+static int ps_run(ftz_ctx* c, size_t n, const PsIn* items, int32_t* codes) {
+  std::lock_guard<std::mutex> lk(c->ps_mu);
+  HC(hipSetDevice(c->device));
+  if (!c->ps) {
+    ftz_batch* b = new ftz_batch();
+    b->ctx = c;
+    int rc = slot_init(b);
+    if (rc != FTZ_SUCCESS) {
+      slot_free(b);
+      delete b;
+      return rc;
+    }
+    c->ps = b;
+  }
+  ftz_batch* b = c->ps;
+  const size_t B = 4 * (size_t)std::max<uint32_t>(c->opt.batch, 1);
+  for (size_t lo = 0; lo < n; lo += B) {
+    const size_t cnt = std::min(B, n - lo);
+    int rc = slot_plan_ps(b, cnt, items + lo);
+    if (rc == FTZ_SUCCESS) rc = slot_submit(b, true, true);
+    if (rc == FTZ_SUCCESS) rc = slot_wait(b);
+    if (rc != FTZ_SUCCESS) return rc;
+    memcpy(codes + lo, slot_codes(b), cnt * sizeof(int32_t));
+  }
+  return FTZ_SUCCESS;
+}
+
+extern "C" int ftz_verify_ps_signatures(ftz_ctx* c, size_t n, const ftz_ps_sig* sigs, int32_t* codes) {
+  if (!c || (n && (!sigs || !codes))) return set_err(FTZ_E_INVALID, "null argument");
+  if (n == 0) return FTZ_SUCCESS;
+  std::vector<PsIn> items(n);
+  for (size_t i = 0; i < n; i++) items[i] = {sigs[i].m, sigs[i].h, sigs[i].r, sigs[i].s};
+  return ps_run(c, n, items.data(), codes);
+}
+
+extern "C" int ftz_pp_audit_signed_values(ftz_ctx* c, int32_t* codes, size_t cap, size_t* count) {
+  if (!c || !count) return set_err(FTZ_E_INVALID, "null argument");
+  const size_t n = c->pp.sig_r.size();
+  *count = n;
+  if (cap < n) return set_err(FTZ_E_INVALID, "codes buffer too small for the signed values");
+  if (n == 0) return FTZ_SUCCESS;
+  if (!codes) return set_err(FTZ_E_INVALID, "null argument");
+  if (c->pp.sig_s.size() != n || c->pp_g1.size() != G1B_COUNT + 2 * n)
+    return set_err(FTZ_E_PP, "signature points not decoded");
+  // entry i as ftz_ctx_create decoded it: the element bytes zero-padded to 64
+  std::vector<ftz_ps_sig> sigs(n);
+  std::vector<PsIn> items(n);
+  for (size_t i = 0; i < n; i++) {
+    ftz_ps_sig& g = sigs[i];
+    memset(&g, 0, sizeof(g));
+    ps_hash_index(i, g.m, g.h);
+    memcpy(g.r, c->pp.sig_r[i].data(), std::min<size_t>(64, c->pp.sig_r[i].size()));
+    memcpy(g.s, c->pp.sig_s[i].data(), std::min<size_t>(64, c->pp.sig_s[i].size()));
+    items[i] = {g.m, g.h, g.r, g.s};
+  }
+  int rc = ps_run(c, n, items.data(), codes);
+  if (rc != FTZ_SUCCESS) return rc;
+  // stricter than Verify: a signature holding the point at infinity signs nothing
+  auto inf = [](const G1Dev& d) {
+    uint32_t o = 0;
+    for (int k = 0; k < 8; k++) o |= d.x[k] | d.y[k];
+    return o == 0;
+  };
+  for (size_t i = 0; i < n; i++)
+    if (inf(c->pp_g1[G1B_COUNT + 2 * i]) || inf(c->pp_g1[G1B_COUNT + 2 * i + 1])) codes[i] = FTZ_ERR_PS_SIGNATURE;
+  return FTZ_SUCCESS;
 }

@@ -237,6 +237,38 @@ class Context:
         _check(self._lib.ftz_audit_openings(self._h, n, coms, arr, codes), self._lib)
         return list(codes)[:n]
 
+    def verify_ps_signatures(self, items):
+        """Pointcheval-Sanders verification (pssign.SignVerifier.Verify) against the
+        context's SignPK / Q.  items: (m, R, S) or (m, h, R, S) with m, h ints or 32
+        bytes and R, S 64-byte G1 encodings; a missing h is HashToZr(m's bytes).
+        Returns a list of codes: 0, FTZ_ERR_PARSE or FTZ_ERR_PS_SIGNATURE."""
+        return [int(c) for c in self.verify_ps_signatures_packed(_abi.pack_ps_sigs(items))]
+
+    def verify_ps_signatures_packed(self, arr):
+        """the same for already packed ftz_ps_sig records (a C-contiguous numpy
+        uint8 array of n x 192 bytes, _abi.pack_ps_sigs); returns numpy int32 codes"""
+        import numpy as np
+        if arr.dtype != np.uint8 or arr.ndim != 2 or arr.shape[1] != 192 or not arr.flags["C_CONTIGUOUS"]:
+            raise ValueError("packed PS signatures are a C-contiguous uint8 array of n x 192 bytes")
+        n = arr.shape[0]
+        codes = np.zeros(max(1, n), dtype=np.int32)
+        _check(self._lib.ftz_verify_ps_signatures(self._h, n, arr.ctypes.data if n else None,
+                                                  codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), self._lib)
+        return codes[:n]
+
+    def audit_signed_values(self):
+        """ftz_pp_audit_signed_values: one code per RangeProofParams.SignedValues
+        entry (0, or FTZ_ERR_PS_SIGNATURE: not a signature on its index, or a
+        point at infinity)"""
+        count = ctypes.c_size_t()
+        rc = self._lib.ftz_pp_audit_signed_values(self._h, None, 0, ctypes.byref(count))
+        if count.value == 0:
+            _check(rc, self._lib)
+            return []
+        codes = (ctypes.c_int32 * count.value)()
+        _check(self._lib.ftz_pp_audit_signed_values(self._h, codes, count.value, ctypes.byref(count)), self._lib)
+        return list(codes)
+
     def msm_g1(self, points, scalars):
         """sum_i k_i P_i (gnark G1Jac.MultiExp semantics): points n x 64-byte
         RawBytes, scalars n x 32 bytes big-endian.  Returns 64-byte RawBytes."""

@@ -223,6 +223,49 @@ GET_STATE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, 
                                 ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t))
 GET_STATES_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p)
 FTZ_ERR_INPUT = 8
+FTZ_ERR_PS_SIGNATURE = 14
+MESSAGES[FTZ_ERR_PS_SIGNATURE] = "invalid Pointcheval-Sanders signature"
+
+
+class PsSig(ctypes.Structure):
+    """ftz_ps_sig: m, h 32 bytes big-endian; r, s 64-byte gnark G1 encodings"""
+    _fields_ = [("m", ctypes.c_uint8 * 32), ("h", ctypes.c_uint8 * 32), ("r", ctypes.c_uint8 * 64),
+                ("s", ctypes.c_uint8 * 64)]
+
+
+def _zr_arg(v):
+    if isinstance(v, int):
+        return v.to_bytes(32, "big")
+    v = bytes(v)
+    if len(v) != 32:
+        raise ValueError("a Zr value is an int or 32 bytes")
+    return v
+
+
+def pack_ps_sigs(items):
+    """items: iterable of (m, R, S) or (m, h, R, S); m, h ints or 32 bytes, R, S
+    64 bytes; a missing h is HashToZr(m's 32 bytes) (pssign hashMessages).
+    Returns a numpy uint8 array of n x 192 bytes (the ftz_ps_sig records)."""
+    import hashlib
+
+    import numpy as np
+    R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+    out = bytearray()
+    n = 0
+    for it in items:
+        if len(it) == 3:
+            m, r, s = it
+            m = _zr_arg(m)
+            h = (int.from_bytes(hashlib.sha256(m).digest(), "big") % R_ORDER).to_bytes(32, "big")
+        else:
+            m, h, r, s = it
+            m, h = _zr_arg(m), _zr_arg(h)
+        r, s = bytes(r), bytes(s)
+        if len(r) != 64 or len(s) != 64:
+            raise ValueError("R and S are 64-byte G1 encodings")
+        out += m + h + r + s
+        n += 1
+    return np.frombuffer(bytes(out), dtype=np.uint8).reshape(n, 192).copy()
 
 
 def pack_bytes(items):
@@ -382,7 +425,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "lib
 # every symbol include/ftsamd.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["ftz_options_default", "ftz_ctx_create", "ftz_ctx_create_ex", "ftz_ctx_destroy", "ftz_last_error",
            "ftz_ctx_set_threads", "ftz_ctx_set_serial", "ftz_ctx_debug_poison", "ftz_ctx_set_debug", "ftz_ctx_set_layout", "ftz_ctx_info", "ftz_ctx_options", "ftz_ctx_engine_stats", "ftz_ctx_debug_engine_sets", "ftz_pp_validate", "ftz_pp_setup",
-           "ftz_commit_tokens", "ftz_audit_openings",
+           "ftz_commit_tokens", "ftz_audit_openings", "ftz_verify_ps_signatures", "ftz_pp_audit_signed_values",
            "ftz_verify_transfers", "ftz_verify_issues", "ftz_batch_load_transfers", "ftz_batch_load_issues",
            "ftz_batch_run", "ftz_batch_submit", "ftz_batch_wait", "ftz_batch_codes", "ftz_batch_bitmap", "ftz_batch_stats", "ftz_batch_size",
            "ftz_batch_destroy", "ftz_batch_challenges", "ftz_msm_g1", "ftz_msm_load", "ftz_msm_load_gen", "ftz_msm_run", "ftz_msm_set_scalars", "ftz_msm_run_scalars", "ftz_host_alloc", "ftz_host_free", "ftz_msm_info", "ftz_msm_destroy", "ftz_g1_sum",
@@ -439,6 +482,8 @@ def load():
     lib.ftz_commit_tokens.argtypes = [vp, sz, ctypes.POINTER(TokenOpening), ctypes.POINTER(ctypes.c_uint8)]
     lib.ftz_audit_openings.argtypes = [vp, sz, ctypes.c_char_p, ctypes.POINTER(TokenOpening),
                                        ctypes.POINTER(ctypes.c_int32)]
+    lib.ftz_verify_ps_signatures.argtypes = [vp, sz, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+    lib.ftz_pp_audit_signed_values.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(sz)]
     lib.ftz_ctx_engine_stats.argtypes = [vp, ctypes.POINTER(EngineStats), ctypes.c_int]
     lib.ftz_ctx_debug_engine_sets.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(sz),
                                               ctypes.POINTER(ctypes.c_uint64)]

@@ -326,6 +326,34 @@ int ftz_commit_tokens(ftz_ctx* ctx, size_t n, const ftz_token_opening* t, uint8_
 int ftz_audit_openings(ftz_ctx* ctx, size_t n, const uint8_t* commitments, const ftz_token_opening* t,
                        int32_t* codes);
 
+/* ---- Pointcheval-Sanders signature verification (crypto/pssign/sign.go:125-160
+ * SignVerifier.Verify, for one message) against the context's SignPK / Q:
+ *   H = PK0 + m PK1 + h PK2,  accept iff FExp(e(-S, Q) e(R, H)) is one in GT.
+ * h is NOT recomputed (the reference's callers pass HashToZr(m.Bytes())).  m and
+ * h are 32 big-endian bytes taken like every other Zr input (big.Int SetBytes,
+ * then reduced mod r for scalar use): m + r verifies as m does.  r and s are
+ * 64-byte gnark G1 encodings under the decoding rules of every other element
+ * (flags, compressed forms, (0,0) = infinity, on-curve check).  A pair holding
+ * a point at infinity is skipped by the Miller loop, as everywhere in this
+ * library [EXT]: R = S = O is accepted, R = O alone (S != O) is rejected.
+ * codes[i] = FTZ_OK (the reference returns nil), FTZ_ERR_PARSE (r or s does
+ * not decode) or FTZ_ERR_PS_SIGNATURE.  Thread-safe; any n (tiled into passes
+ * of at most 4 x ftz_options.batch items); n = 0 succeeds. */
+#define FTZ_ERR_PS_SIGNATURE 14 /* invalid Pointcheval-Sanders signature */
+typedef struct {
+  uint8_t m[32], h[32], r[64], s[64];
+} ftz_ps_sig;
+int ftz_verify_ps_signatures(ftz_ctx* ctx, size_t n, const ftz_ps_sig* sigs, int32_t* codes);
+/* Audit of RangeProofParams.SignedValues: entry i must be a signature on m = i
+ * with h = HashToZr(32-byte big-endian i), which is what
+ * GenerateRangeProofParameters signs (setup.go:168-184).  Always writes *count
+ * = len(SignedValues); with cap >= *count, codes[i] = FTZ_OK or
+ * FTZ_ERR_PS_SIGNATURE -- also for an entry whose R or S is the point at
+ * infinity, which the item call above would skip (an audit has no reference
+ * behaviour to mirror).  cap < *count: FTZ_E_INVALID after writing *count.
+ * Neither ftz_pp_validate nor ftz_ctx_create runs this check. */
+int ftz_pp_audit_signed_values(ftz_ctx* ctx, int32_t* codes, size_t cap, size_t* count);
+
 /* ---- raw token requests (the wire format around the path).
  * A request is asn1.Marshal(driver.TokenRequest{Issues, Transfers, Signatures,
  * AuditorSignatures [][]byte}) (token/driver/request.go:24-38). */
