@@ -2,37 +2,31 @@
 // the auditor's and the issuers' signatures of a token request, and fabtoken
 // owners.  Identities and DER signatures are decoded on the host pool
 // (host/x509id.cpp); SHA-256 of the message, s^-1 and the curve arithmetic run
-// on the GPU (k_ecdsa_pre / _part / _fin, dev/p256.h).  Mirrors idemix_rt.hip.
+// on the GPU (k_ecdsa_pre / _part / _fin, dev/p256.h).  The second half signs.
+// Both calls run their chunks through the two-slot driver of host/sigpipe.h.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <map>
 #include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "ecdsa_k.h"
 #include "ecsign_k.h"
 #include "host/x509id.h"
-#include "rt_internal.h"
+#include "sigpipe_rt.h"
 
-// One pipeline slot: pinned staging, device blob / scalars / partials / verdicts, its stream.
-struct EcdsaSlot {
+// One pipeline slot: pinned staging, device blob / scalars / partials / verdicts.
+struct EcdsaSlot : SigSlot {
   PinnedMem h_blob, h_ok;
   DevMem d_blob, d_ok, d_u, d_part, d_vt;
-  hipStream_t st = nullptr;
-  std::vector<uint32_t> idx;  // call-relative indices of the slot's signatures
-  bool busy = false;
 };
 
-// One pipeline slot of the signer: pinned staging, device blob / nonces / digests / partials / r || s, its stream.
-struct EcsignSlot {
+// One pipeline slot of the signer: pinned staging, device blob / nonces / digests / partials / r || s.
+struct EcsignSlot : SigSlot {
   PinnedMem h_blob, h_out;
   DevMem d_blob, d_out, d_k, d_e, d_part;
-  hipStream_t st = nullptr;
-  size_t a = 0, m = 0;  // the slot's signatures: call-relative [a, a + m)
-  bool busy = false;
 };
 
 struct ftz_ecdsa {
@@ -42,31 +36,20 @@ struct ftz_ecdsa {
   int32_t n_keys = 0;
   std::mutex mu;                       // one call on the device at a time
   WorkPool* pool = nullptr;            // host decoding threads
-  EcdsaSlot slot[2];                   // chunk k+1 is decoded and laid out while chunk k runs
+  EcdsaSlot slot[2];
   // signing (ftz_ecdsa_add_signer / ftz_sign_ecdsa): the private scalars live on the device only
   std::vector<P256Aff> gtab;           // host copy of table 0 (public keys of new signers)
-  DBuf<uint32_t> skeys;                // ECSIGN_MAX_SIGNERS x 8 limbs, allocated with the first signer
-  int32_t n_signers = 0;
+  SignerKeys signers;                  // ECSIGN_MAX_SIGNERS of them
   EcsignSlot sslot[2];                 // streams created by the first signing call
   ~ftz_ecdsa() {
-    for (EcsignSlot& q : sslot)
-      if (q.st) {
-        (void)hipStreamSynchronize(q.st);
-        (void)hipStreamDestroy(q.st);
-      }
-    if (skeys.p) (void)hipMemset(skeys.p, 0, skeys.n * sizeof(uint32_t));
-    for (EcdsaSlot& q : slot)
-      if (q.st) {
-        (void)hipStreamSynchronize(q.st);
-        (void)hipStreamDestroy(q.st);
-      }
+    for (EcsignSlot& q : sslot) q.close();  // no signing pass reads the keys any more
+    signers.wipe();
+    for (EcdsaSlot& q : slot) q.close();
     delete pool;
   }
 };
 
 namespace {
-constexpr size_t ECDSA_CHUNK_BYTES = (size_t)1 << 30;  // keeps every blob offset in 32 bits
-constexpr size_t ECDSA_CHUNK_SIGS = 4096;              // signatures per pipelined device pass
 constexpr size_t ECDSA_ITEM_BYTES = 16 + ECDSA_SC_BYTES + 16;  // job, scalars / key, message alignment
 
 void table_of(const uint8_t xy[64], std::vector<P256Aff>& tab) {
@@ -82,27 +65,16 @@ struct EcdsaDecoded {
   uint8_t r[32], s[32], xy[64];
 };
 
-// collect the verdicts of a slot's pass
-int ecdsa_collect(EcdsaSlot& q, int32_t* codes) {
-  if (!q.busy) return FTZ_SUCCESS;
-  q.busy = false;
-  HC(hipStreamSynchronize(q.st));
-  for (size_t k = 0; k < q.idx.size(); k++) codes[q.idx[k]] = q.h_ok.p[k] ? FTZ_OK : FTZ_ERR_SIGNATURE;
-  return FTZ_SUCCESS;
-}
-
 // decode s[a..b) on the pool; queue the device pass of the ones that reach the curve arithmetic
 int ecdsa_chunk(ftz_ecdsa* e, EcdsaSlot& q, const ftz_ecdsa_sig* s, size_t a, size_t b, int32_t* codes) {
   size_t n = b - a;
   std::vector<EcdsaDecoded> dec(n);
-  e->pool->run((n + 63) / 64, [&](size_t p) {
-    for (size_t i = p * 64; i < n && i < (p + 1) * 64; i++) {
-      const ftz_ecdsa_sig& it = s[a + i];
-      EcdsaDecoded& d = dec[i];
-      // the verifier is deserialized first (identity errors), then Verify unmarshals the signature
-      if (it.key < 0) d.code = ftsh::decode_x509_identity(it.identity, it.identity_len, d.xy);
-      if (d.code == 0) d.code = ftsh::decode_ecdsa_signature(it.sig, it.sig_len, d.r, d.s);
-    }
+  par_for(e->pool, n, [&](size_t i) {
+    const ftz_ecdsa_sig& it = s[a + i];
+    EcdsaDecoded& d = dec[i];
+    // the verifier is deserialized first (identity errors), then Verify unmarshals the signature
+    if (it.key < 0) d.code = ftsh::decode_x509_identity(it.identity, it.identity_len, d.xy);
+    if (d.code == 0) d.code = ftsh::decode_ecdsa_signature(it.sig, it.sig_len, d.r, d.s);
   });
   // registered-key jobs first, then the ad-hoc ones (k_ecdsa_part's lane ranges)
   std::vector<uint32_t> idx;  // chunk-relative
@@ -115,30 +87,12 @@ int ecdsa_chunk(ftz_ecdsa* e, EcdsaSlot& q, const ftz_ecdsa_sig* s, size_t a, si
     if (dec[i].code == 0 && s[a + i].key < 0) idx.push_back((uint32_t)i);
   if (idx.empty()) return FTZ_SUCCESS;
   size_t m = idx.size();
-  // blob: jobs | r, s, Qx, Qy per job | every distinct message (same pointer and length) once, 16-aligned
-  std::vector<EcdsaJob> jobs(m);
-  std::vector<uint8_t> copies(m, 0);
-  std::unordered_map<const uint8_t*, std::pair<uint32_t, uint32_t>> seen;  // pointer -> (offset, length)
-  size_t off = (m * sizeof(EcdsaJob) + 15) & ~(size_t)15;
-  for (size_t k = 0; k < m; k++) {
-    jobs[k].sc = (uint32_t)off;
-    off += ECDSA_SC_BYTES;
-  }
-  for (size_t k = 0; k < m; k++) {
-    const ftz_ecdsa_sig& it = s[a + idx[k]];
-    jobs[k].msg_len = (uint32_t)it.msg_len;
-    jobs[k].key = it.key >= 0 ? it.key + 1 : -1;
-    auto f = it.msg_len ? seen.find(it.msg) : seen.end();
-    if (f != seen.end() && f->second.second == it.msg_len) {
-      jobs[k].msg = f->second.first;
-      continue;
-    }
-    jobs[k].msg = (uint32_t)off;
-    copies[k] = 1;
-    if (it.msg_len) seen[it.msg] = {(uint32_t)off, (uint32_t)it.msg_len};
-    off += (it.msg_len + 15) & ~(size_t)15;
-  }
-  size_t total = off + 64;  // slack: the SHA-256 block loads never leave the buffer
+  // blob: jobs | r, s, Qx, Qy per job | every distinct message once, 16-aligned
+  const size_t sc_at = (m * sizeof(EcdsaJob) + 15) & ~(size_t)15;
+  auto msg = [&](size_t k) { return std::make_pair(s[a + idx[k]].msg, s[a + idx[k]].msg_len); };
+  MsgLayout L;
+  sig_layout_messages(m, sc_at + m * ECDSA_SC_BYTES, 0, msg, L);
+  size_t total = L.end + 64;  // slack: the SHA-256 block loads never leave the buffer
   HC(q.h_blob.reserve(total));
   HC(q.d_blob.reserve(total));
   HC(q.h_ok.reserve(m));
@@ -147,25 +101,29 @@ int ecdsa_chunk(ftz_ecdsa* e, EcdsaSlot& q, const ftz_ecdsa_sig* s, size_t a, si
   HC(q.d_part.reserve(2 * m * sizeof(P256Jac)));
   HC(q.d_vt.reserve((m - n_reg + 1) * P256_VT_WORDS * sizeof(uint32_t)));
   uint8_t* blob = q.h_blob.p;
-  memcpy(blob, jobs.data(), m * sizeof(EcdsaJob));
-  e->pool->run((m + 63) / 64, [&](size_t p) {
-    for (size_t k = p * 64; k < m && k < (p + 1) * 64; k++) {
-      const EcdsaDecoded& d = dec[idx[k]];
-      const ftz_ecdsa_sig& it = s[a + idx[k]];
-      uint8_t* sc = blob + jobs[k].sc;
-      memcpy(sc, d.r, 32);
-      memcpy(sc + 32, d.s, 32);
-      if (it.key < 0)
-        memcpy(sc + 64, d.xy, 64);
-      else
-        memset(sc + 64, 0, 64);
-      if (copies[k] && it.msg_len) memcpy(blob + jobs[k].msg, it.msg, it.msg_len);
-    }
+  par_for(e->pool, m + L.distinct.size(), [&](size_t k) {  // the jobs, then the messages
+    if (k >= m) return sig_copy_message(L, k - m, blob, msg);
+    const EcdsaDecoded& d = dec[idx[k]];
+    const ftz_ecdsa_sig& it = s[a + idx[k]];
+    EcdsaJob j;
+    j.sc = (uint32_t)(sc_at + k * ECDSA_SC_BYTES);
+    j.msg = L.msg_off[k];
+    j.msg_len = (uint32_t)it.msg_len;
+    j.key = it.key >= 0 ? it.key + 1 : -1;
+    memcpy(blob + k * sizeof(EcdsaJob), &j, sizeof j);
+    uint8_t* sc = blob + j.sc;
+    memcpy(sc, d.r, 32);
+    memcpy(sc + 32, d.s, 32);
+    if (it.key < 0)
+      memcpy(sc + 64, d.xy, 64);
+    else
+      memset(sc + 64, 0, 64);
   });
   const EcdsaJob* djobs = reinterpret_cast<const EcdsaJob*>(q.d_blob.p);
   uint32_t(*du)[8] = reinterpret_cast<uint32_t(*)[8]>(q.d_u.p);
   P256Jac* part = reinterpret_cast<P256Jac*>(q.d_part.p);
-  HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, off, hipMemcpyHostToDevice, q.st));
+  sig_pass_begin(q, a, idx.data(), m);
+  HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, L.end, hipMemcpyHostToDevice, q.st));
   const uint32_t g1 = (uint32_t)((m + 63) / 64), g2 = (uint32_t)((2 * m + 63) / 64);
   k_ecdsa_pre<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, q.d_blob.p, du, q.d_ok.p);
   k_ecdsa_part<<<g2, 64, 0, q.st>>>(djobs, (uint32_t)m, (uint32_t)n_reg, q.d_blob.p, du, e->tabs.p,
@@ -173,9 +131,7 @@ int ecdsa_chunk(ftz_ecdsa* e, EcdsaSlot& q, const ftz_ecdsa_sig* s, size_t a, si
   k_ecdsa_fin<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, q.d_blob.p, part, q.d_ok.p);
   HC(hipGetLastError());
   HC(hipMemcpyAsync(q.h_ok.p, q.d_ok.p, m, hipMemcpyDeviceToHost, q.st));
-  q.idx.resize(m);
-  for (size_t k = 0; k < m; k++) q.idx[k] = (uint32_t)(a + idx[k]);
-  q.busy = true;
+  q.enqueued = true;
   return FTZ_SUCCESS;
 }
 }  // namespace
@@ -195,7 +151,7 @@ extern "C" int ftz_ecdsa_create(ftz_ctx* ctx, ftz_ecdsa** out) {
   e->ctx = ctx;
   e->pool = new WorkPool(ctx->opt.threads ? (int)ctx->opt.threads : 8);
   for (EcdsaSlot& q : e->slot) {
-    hipError_t se = hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking);
+    hipError_t se = q.open();
     if (se != hipSuccess) {
       delete e;
       return set_err(FTZ_E_DEVICE, std::string("hipStreamCreate failed: ") + hipGetErrorString(se));
@@ -256,33 +212,15 @@ extern "C" int ftz_verify_ecdsa_signatures(ftz_ecdsa* e, size_t n, const ftz_ecd
     if ((s[i].key < 0 && !s[i].identity && s[i].identity_len) || (!s[i].msg && s[i].msg_len) ||
         (!s[i].sig && s[i].sig_len))
       return set_err(FTZ_E_INVALID, "null buffer with non-zero length");
-    if (s[i].msg_len > ECDSA_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
+    if (s[i].msg_len > ftsh::SIG_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
     if (s[i].key < -1 || s[i].key >= e->n_keys)
       return set_err(FTZ_E_INVALID, "key " + std::to_string(s[i].key) + " is not a registered key");
   }
   HC(hipSetDevice(e->ctx->device));
-  // chunks of <= ECDSA_CHUNK_SIGS signatures and < ECDSA_CHUNK_BYTES of blob, alternating
-  // between the two slots: chunk k+1 is decoded and laid out while chunk k runs
-  size_t a = 0, c = 0;
-  int rc = FTZ_SUCCESS;
-  while (a < n && rc == FTZ_SUCCESS) {
-    size_t b = a, bytes = 0;
-    while (b < n && b - a < ECDSA_CHUNK_SIGS &&
-           (b == a || bytes + s[b].msg_len + ECDSA_ITEM_BYTES < ECDSA_CHUNK_BYTES)) {
-      bytes += s[b].msg_len + ECDSA_ITEM_BYTES;
-      b++;
-    }
-    EcdsaSlot& q = e->slot[c & 1];
-    rc = ecdsa_collect(q, codes);
-    if (rc == FTZ_SUCCESS) rc = ecdsa_chunk(e, q, s, a, b, codes);
-    a = b;
-    c++;
-  }
-  for (EcdsaSlot& q : e->slot) {
-    int r2 = ecdsa_collect(q, codes);
-    if (rc == FTZ_SUCCESS) rc = r2;
-  }
-  return rc;
+  return ftsh::sig_run(
+      n, ftsh::SIG_CHUNK_ITEMS, ftsh::SIG_CHUNK_BYTES, [&](size_t i) { return s[i].msg_len + ECDSA_ITEM_BYTES; },
+      [&](int k) { return sig_collect_verdicts(e->slot[k], e->slot[k].h_ok.p, codes); },
+      [&](int k, size_t a, size_t b) { return ecdsa_chunk(e, e->slot[k], s, a, b, codes); });
 }
 
 // ------------------------------------------------------------------ signing
@@ -296,22 +234,27 @@ static_assert(ECSIGN_MAX_SIGNERS == FTZ_ECDSA_MAX_SIGNERS, "the device array hol
 // wait for a slot's pass and write its DER signatures
 int ecsign_collect(ftz_ecdsa* e, EcsignSlot& q, uint8_t* sigs, uint32_t* sig_lens, int32_t* codes) {
   if (!q.busy) return FTZ_SUCCESS;
-  q.busy = false;
-  HC(hipStreamSynchronize(q.st));
+  int rc = sig_pass_end(q);
+  const size_t m = q.idx.size();
+  if (rc != FTZ_SUCCESS) {  // the wipes the pass ends with may not have run
+    (void)hipMemset(q.d_k.p, 0, m * 32);
+    (void)hipMemset(q.d_e.p, 0, m * 32);
+    (void)hipMemset(q.d_part.p, 0, ECSIGN_PARTS * m * sizeof(P256Jac));
+    return rc;
+  }
   const uint8_t* rs = q.h_out.p;
-  const uint8_t* ok = q.h_out.p + q.m * 64;
-  e->pool->run((q.m + 63) / 64, [&](size_t p) {
-    for (size_t k = p * 64; k < q.m && k < (p + 1) * 64; k++) {
-      uint8_t* out = sigs + (q.a + k) * FTZ_ECDSA_SIG_MAX;
-      memset(out, 0, FTZ_ECDSA_SIG_MAX);
-      if (!ok[k]) {
-        sig_lens[q.a + k] = 0;
-        codes[q.a + k] = FTZ_ERR_SIGNATURE;
-        continue;
-      }
-      sig_lens[q.a + k] = (uint32_t)ftsh::encode_ecdsa_signature(rs + k * 64, rs + k * 64 + 32, out);
-      codes[q.a + k] = FTZ_OK;
+  const uint8_t* ok = q.h_out.p + m * 64;
+  par_for(e->pool, m, [&](size_t k) {
+    const size_t i = q.idx[k];
+    uint8_t* out = sigs + i * FTZ_ECDSA_SIG_MAX;
+    memset(out, 0, FTZ_ECDSA_SIG_MAX);
+    if (!ok[k]) {
+      sig_lens[i] = 0;
+      codes[i] = FTZ_ERR_SIGNATURE;
+      return;
     }
+    sig_lens[i] = (uint32_t)ftsh::encode_ecdsa_signature(rs + k * 64, rs + k * 64 + 32, out);
+    codes[i] = FTZ_OK;
   });
   return FTZ_SUCCESS;
 }
@@ -319,31 +262,20 @@ int ecsign_collect(ftz_ecdsa* e, EcsignSlot& q, uint8_t* sigs, uint32_t* sig_len
 // lay out it[a..b) and queue its device pass
 int ecsign_chunk(ftz_ecdsa* e, EcsignSlot& q, const ftz_ecdsa_sign_item* it, size_t a, size_t b) {
   const size_t m = b - a;
-  // blob: jobs | every distinct message (same pointer and length) once, 16-aligned | 32 entropy bytes per hedged job
+  // blob: jobs | 32 entropy bytes per hedged job | every distinct message once, 16-aligned
   std::vector<EcsignJob> jobs(m);
-  std::vector<uint8_t> copies(m, 0);
-  std::unordered_map<const uint8_t*, std::pair<uint32_t, uint32_t>> seen;  // pointer -> (offset, length)
   size_t off = (m * sizeof(EcsignJob) + 15) & ~(size_t)15;
   for (size_t k = 0; k < m; k++) {
-    const ftz_ecdsa_sign_item& s = it[a + k];
-    jobs[k].msg_len = (uint32_t)s.msg_len;
-    jobs[k].signer = s.signer;
     jobs[k].entropy = 0;
-    if (s.entropy) {
+    if (it[a + k].entropy) {
       jobs[k].entropy = (uint32_t)off;
       off += 32;
     }
-    auto f = s.msg_len ? seen.find(s.msg) : seen.end();
-    if (f != seen.end() && f->second.second == s.msg_len) {
-      jobs[k].msg = f->second.first;
-      continue;
-    }
-    jobs[k].msg = (uint32_t)off;
-    copies[k] = 1;
-    if (s.msg_len) seen[s.msg] = {(uint32_t)off, (uint32_t)s.msg_len};
-    off += (s.msg_len + 15) & ~(size_t)15;
   }
-  const size_t total = off + 64;  // slack: the SHA-256 block loads never leave the buffer
+  auto msg = [&](size_t k) { return std::make_pair(it[a + k].msg, it[a + k].msg_len); };
+  MsgLayout L;
+  sig_layout_messages(m, off, 0, msg, L);
+  const size_t total = L.end + 64;  // slack: the SHA-256 block loads never leave the buffer
   HC(q.h_blob.reserve(total));
   HC(q.d_blob.reserve(total));
   HC(q.h_out.reserve(m * 65));
@@ -352,26 +284,27 @@ int ecsign_chunk(ftz_ecdsa* e, EcsignSlot& q, const ftz_ecdsa_sign_item* it, siz
   HC(q.d_e.reserve(m * 32));
   HC(q.d_part.reserve(ECSIGN_PARTS * m * sizeof(P256Jac)));
   uint8_t* blob = q.h_blob.p;
-  memcpy(blob, jobs.data(), m * sizeof(EcsignJob));
-  e->pool->run((m + 63) / 64, [&](size_t p) {
-    for (size_t k = p * 64; k < m && k < (p + 1) * 64; k++) {
-      const ftz_ecdsa_sign_item& s = it[a + k];
-      if (s.entropy) memcpy(blob + jobs[k].entropy, s.entropy, 32);
-      if (copies[k] && s.msg_len) memcpy(blob + jobs[k].msg, s.msg, s.msg_len);
-    }
+  par_for(e->pool, m + L.distinct.size(), [&](size_t k) {  // the jobs, then the messages
+    if (k >= m) return sig_copy_message(L, k - m, blob, msg);
+    const ftz_ecdsa_sign_item& s = it[a + k];
+    jobs[k].msg = L.msg_off[k];
+    jobs[k].msg_len = (uint32_t)s.msg_len;
+    jobs[k].signer = s.signer;
+    memcpy(blob + k * sizeof(EcsignJob), &jobs[k], sizeof(EcsignJob));
+    if (s.entropy) memcpy(blob + jobs[k].entropy, s.entropy, 32);
   });
   const EcsignJob* djobs = reinterpret_cast<const EcsignJob*>(q.d_blob.p);
-  const uint32_t(*keys)[8] = reinterpret_cast<const uint32_t(*)[8]>(e->skeys.p);
   uint32_t(*dk)[8] = reinterpret_cast<uint32_t(*)[8]>(q.d_k.p);
   uint32_t(*de)[8] = reinterpret_cast<uint32_t(*)[8]>(q.d_e.p);
   P256Jac* part = reinterpret_cast<P256Jac*>(q.d_part.p);
   uint8_t* d_rs = q.d_out.p;
   uint8_t* d_ok = q.d_out.p + m * 64;
-  HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, off, hipMemcpyHostToDevice, q.st));
+  sig_pass_begin(q, a, nullptr, m);
+  HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, L.end, hipMemcpyHostToDevice, q.st));
   const uint32_t g1 = (uint32_t)((m + 63) / 64), g4 = (uint32_t)((ECSIGN_PARTS * m + 63) / 64);
-  k_ecsign_pre<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, q.d_blob.p, keys, dk, de);
+  k_ecsign_pre<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, q.d_blob.p, e->signers.keys(), dk, de);
   k_ecsign_part<<<g4, 64, 0, q.st>>>((uint32_t)m, dk, e->tabs.p, part);
-  k_ecsign_fin<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, keys, part, dk, de, d_rs, d_ok);
+  k_ecsign_fin<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, e->signers.keys(), part, dk, de, d_rs, d_ok);
   HC(hipGetLastError());
   HC(hipMemcpyAsync(q.h_out.p, q.d_out.p, m * 65, hipMemcpyDeviceToHost, q.st));
   // nothing secret stays behind the pass: the nonces (k_ecsign_fin has zeroed its own), the digests
@@ -379,9 +312,7 @@ int ecsign_chunk(ftz_ecdsa* e, EcsignSlot& q, const ftz_ecdsa_sign_item* it, siz
   HC(hipMemsetAsync(q.d_k.p, 0, m * 32, q.st));
   HC(hipMemsetAsync(q.d_e.p, 0, m * 32, q.st));
   HC(hipMemsetAsync(q.d_part.p, 0, ECSIGN_PARTS * m * sizeof(P256Jac), q.st));
-  q.a = a;
-  q.m = m;
-  q.busy = true;
+  q.enqueued = true;
   return FTZ_SUCCESS;
 }
 }  // namespace
@@ -397,15 +328,10 @@ extern "C" int ftz_ecdsa_add_signer(ftz_ecdsa* e, const uint8_t d[32], int32_t* 
   std::lock_guard<std::mutex> lk(e->mu);
   int rc = FTZ_SUCCESS;
   hipError_t he = hipSuccess;
-  if (e->n_signers >= ECSIGN_MAX_SIGNERS) {
+  if (e->signers.n >= ECSIGN_MAX_SIGNERS) {
     rc = set_err(FTZ_E_INVALID, "too many signers (at most " + std::to_string(ECSIGN_MAX_SIGNERS) + ")");
   } else {
-    he = hipSetDevice(e->ctx->device);
-    if (he == hipSuccess && !e->skeys.p) {
-      he = e->skeys.alloc((size_t)ECSIGN_MAX_SIGNERS * 8);
-      if (he == hipSuccess) he = hipMemset(e->skeys.p, 0, e->skeys.n * sizeof(uint32_t));
-    }
-    if (he == hipSuccess && public_xy) {  // d G on the host; d < n is no multiple of n: never infinity
+    if (public_xy) {  // d G on the host; d < n is no multiple of n: never infinity
       p256j q = p256_fixed_mul(e->gtab.data(), dl);
       pf zi = pf_inv(q.z);
       pf zi2 = pf_sqr(zi);
@@ -415,10 +341,7 @@ extern "C" int ftz_ecdsa_add_signer(ftz_ecdsa* e, const uint8_t d[32], int32_t* 
       pf_to_int(t, q.y * zi2 * zi);
       limbs_to_be32(public_xy + 32, t);
     }
-    // no pass is in flight (a signing call holds the mutex until it has collected its slots)
-    if (he == hipSuccess)
-      he = hipMemcpy(e->skeys.p + (size_t)e->n_signers * 8, dl, sizeof dl, hipMemcpyHostToDevice);
-    if (he == hipSuccess) *signer = e->n_signers++;
+    he = e->signers.add(e->ctx->device, ECSIGN_MAX_SIGNERS, dl, signer);
   }
   explicit_bzero(dl, sizeof dl);
   if (he != hipSuccess) return set_err(FTZ_E_DEVICE, std::string("signer upload failed: ") + hipGetErrorString(he));
@@ -431,34 +354,15 @@ extern "C" int ftz_sign_ecdsa(ftz_ecdsa* e, size_t n, const ftz_ecdsa_sign_item*
   std::lock_guard<std::mutex> lk(e->mu);
   for (size_t i = 0; i < n; i++) {
     if (!it[i].msg && it[i].msg_len) return set_err(FTZ_E_INVALID, "null buffer with non-zero length");
-    if (it[i].msg_len > ECDSA_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
-    if (it[i].signer < 0 || it[i].signer >= e->n_signers)
+    if (it[i].msg_len > ftsh::SIG_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
+    if (it[i].signer < 0 || it[i].signer >= e->signers.n)
       return set_err(FTZ_E_INVALID, "signer " + std::to_string(it[i].signer) + " is not a registered signer");
   }
   if (n == 0) return FTZ_SUCCESS;
   HC(hipSetDevice(e->ctx->device));
-  for (EcsignSlot& q : e->sslot)
-    if (!q.st) HC(hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
-  // chunks of <= ECDSA_CHUNK_SIGS signatures and < ECDSA_CHUNK_BYTES of blob, alternating
-  // between the two slots: chunk k+1 is laid out while chunk k runs
-  size_t a = 0, c = 0;
-  int rc = FTZ_SUCCESS;
-  while (a < n && rc == FTZ_SUCCESS) {
-    size_t b = a, bytes = 0;
-    while (b < n && b - a < ECDSA_CHUNK_SIGS &&
-           (b == a || bytes + it[b].msg_len + ECSIGN_ITEM_BYTES < ECDSA_CHUNK_BYTES)) {
-      bytes += it[b].msg_len + ECSIGN_ITEM_BYTES;
-      b++;
-    }
-    EcsignSlot& q = e->sslot[c & 1];
-    rc = ecsign_collect(e, q, sigs, sig_lens, codes);
-    if (rc == FTZ_SUCCESS) rc = ecsign_chunk(e, q, it, a, b);
-    a = b;
-    c++;
-  }
-  for (EcsignSlot& q : e->sslot) {
-    int r2 = ecsign_collect(e, q, sigs, sig_lens, codes);
-    if (rc == FTZ_SUCCESS) rc = r2;
-  }
-  return rc;
+  for (EcsignSlot& q : e->sslot) HC(q.open());
+  return ftsh::sig_run(
+      n, ftsh::SIG_CHUNK_ITEMS, ftsh::SIG_CHUNK_BYTES, [&](size_t i) { return it[i].msg_len + ECSIGN_ITEM_BYTES; },
+      [&](int k) { return ecsign_collect(e, e->sslot[k], sigs, sig_lens, codes); },
+      [&](int k, size_t a, size_t b) { return ecsign_chunk(e, e->sslot[k], it, a, b); });
 }

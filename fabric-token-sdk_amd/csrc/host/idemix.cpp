@@ -3,8 +3,6 @@
 
 #include <string.h>
 
-#include <map>
-
 #include "../dev/idemix.h"
 #include "gojson.h"
 
@@ -587,23 +585,10 @@ void nym_glv_split_bn(const uint8_t kb[32], uint32_t out[12]) {
 void nym_plan_layout(const ftz_owner_sig* s, const uint32_t* idx, size_t m, NymLayout& L, int curve) {
   constexpr size_t PER_JOB = fts::NYM_SC_BYTES + fts::NYM_PRE_SLOT;
   const size_t align = (curve == FTZ_CURVE_BN254 ? fts::NymCurve<fts::fp>::PRE : fts::NymCurve<fts::fq>::PRE) % 16;
-  size_t off = ((m * sizeof(fts::NymJob) + 15) & ~(size_t)15) + m * PER_JOB;
-  std::map<std::pair<const uint8_t*, size_t>, uint32_t> at;
-  L.msg_off.resize(m);
-  L.distinct.clear();
-  for (size_t k = 0; k < m; k++) {
-    const ftz_owner_sig& q = s[idx[k]];
-    auto key = std::make_pair(q.msg, q.msg_len);
-    auto it = at.find(key);
-    if (it == at.end()) {
-      off = ((off + 15) & ~(size_t)15) + align;
-      it = at.emplace(key, (uint32_t)off).first;
-      L.distinct.push_back({(uint32_t)off, (uint32_t)k});
-      off += q.msg_len;
-    }
-    L.msg_off[k] = it->second;
-  }
-  L.total = off + 64;  // + slack: the hash reads whole 16-byte words
+  sig_layout_messages(m, ((m * sizeof(fts::NymJob) + 15) & ~(size_t)15) + m * PER_JOB, align, [&](size_t k) {
+    return std::make_pair(s[idx[k]].msg, s[idx[k]].msg_len);
+  }, L);
+  L.total = L.end + 64;  // + slack: the hash reads whole 16-byte words
 }
 
 void nym_fill(const ftz_owner_sig* s, const uint32_t* idx, size_t m, const NymDecoded* dec,

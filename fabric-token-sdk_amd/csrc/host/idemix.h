@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../../include/ftsamd.h"
+#include "sigpipe.h"
 
 namespace ftsh {
 
@@ -91,10 +92,8 @@ void decode_owner_audit(const uint8_t* owner, size_t owner_len, const uint8_t* a
 // transcript prefix ("sign", zeros for t and Nym, the IPK hash after them and,
 // on BN254, the 2 tail bytes), then every distinct message (same pointer and
 // length) once at an offset = NymCurve::PRE mod 16 (6 on FP256BN, 4 on BN254).
-struct NymLayout {
-  size_t total = 0;                                   // blob bytes (+ slack)
-  std::vector<uint32_t> msg_off;                      // per job
-  std::vector<std::pair<uint32_t, uint32_t>> distinct;  // (blob offset, job whose message is copied there)
+struct NymLayout : MsgLayout {  // msg_off per job, distinct: (blob offset, job whose message is copied there)
+  size_t total = 0;             // blob bytes (+ slack)
 };
 void nym_plan_layout(const ftz_owner_sig* s, const uint32_t* idx, size_t m, NymLayout& L,
                      int curve = FTZ_CURVE_FP256BN_AMCL);

@@ -3,11 +3,11 @@
 // on the host pool (host/idemix.cpp), NymSignature.Ver's curve arithmetic and
 // hashes on the GPU (k_nym_part/_fin, _bn for BN254; dev/idemix.h).  On BN254
 // the same handle signs: NewNymSignature and MakeNym in batches (k_nymsign_*,
-// dev/nymsign.h), the second half of this file.
+// dev/nymsign.h), the second half of this file.  Both calls run their chunks
+// through the two-slot driver of host/sigpipe.h.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -15,20 +15,17 @@
 #include "host/idemix.h"
 #include "launch.h"
 #include "nymsign_k.h"
-#include "rt_internal.h"
+#include "sigpipe_rt.h"
 
-// One pipeline slot: pinned staging, device blob / partials / verdicts, its stream.
-struct NymSlot {
+// One pipeline slot: pinned staging, device blob / partials / verdicts.  A call holds the handle's mutex
+// until it has collected its passes, so verifying and signing passes share the slots.
+struct NymSlot : SigSlot {
   PinnedMem h_blob, h_ok;
   DevMem d_blob, d_ok, d_part;
-  hipStream_t st = nullptr;
-  std::vector<uint32_t> idx;  // call-relative indices of the slot's signatures
-  bool busy = false;
-  // signing passes on the same slot (a call collects its passes before it returns the mutex)
+  // signing passes
   PinnedMem h_sig;
   DevMem d_sig, d_rand;      // 128 bytes + ok byte per signature; r_sk, r_rnym, nonce
-  size_t sec_at = 0, sec_len = 0;  // the blob's section of RNym values
-  bool sbusy = false;
+  size_t rnym_at = 0;        // the blob's section of RNym values, 32 bytes per item of the pass
 };
 
 struct ftz_idemix {
@@ -46,17 +43,12 @@ struct ftz_idemix {
   NymSlot slot[2];             // chunk k+1 is decoded and laid out while chunk k runs
   // signing (ftz_idemix_add_signer / ftz_sign_owner_signatures / ftz_idemix_make_nyms): the user
   // secrets live on the device only
-  DBuf<uint32_t> skeys;        // NYMSIGN_MAX_SIGNERS x 8 limbs (256 bytes), allocated with the first signer
-  int32_t n_signers = 0;
+  SignerKeys signers;          // NYMSIGN_MAX_SIGNERS of them
   PinnedMem h_mk;              // ftz_idemix_make_nyms staging: RNym values in, nyms out
   DevMem d_mk;
   ~ftz_idemix() {
-    for (NymSlot& q : slot)
-      if (q.st) {
-        (void)hipStreamSynchronize(q.st);
-        (void)hipStreamDestroy(q.st);
-      }
-    if (skeys.p) (void)hipMemset(skeys.p, 0, skeys.n * sizeof(uint32_t));
+    for (NymSlot& q : slot) q.close();
+    signers.wipe();
     delete pool;
   }
 };
@@ -99,7 +91,7 @@ extern "C" int ftz_idemix_create(ftz_ctx* ctx, const uint8_t* ipk, size_t ipk_le
   ix->ctx = ctx;
   ix->pool = new WorkPool(ctx->opt.threads ? (int)ctx->opt.threads : 8);
   for (NymSlot& q : ix->slot) {
-    hipError_t se = hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking);
+    hipError_t se = q.open();
     if (se != hipSuccess) {
       delete ix;
       return set_err(FTZ_E_DEVICE, std::string("hipStreamCreate failed: ") + hipGetErrorString(se));
@@ -129,25 +121,14 @@ extern "C" int ftz_idemix_set_strict_nym(ftz_idemix* ix, int on) {
 }
 
 namespace {
-constexpr size_t NYM_CHUNK_BYTES = (size_t)1 << 30;  // keeps every blob offset in 32 bits
-constexpr size_t NYM_CHUNK_SIGS = 4096;              // signatures per pipelined device pass
-
-// collect the verdicts of a slot's pass
-int nym_collect(NymSlot& q, int32_t* codes) {
-  if (!q.busy) return FTZ_SUCCESS;
-  q.busy = false;
-  HC(hipStreamSynchronize(q.st));
-  for (size_t k = 0; k < q.idx.size(); k++) codes[q.idx[k]] = q.h_ok.p[k] ? FTZ_OK : FTZ_ERR_SIGNATURE;
-  return FTZ_SUCCESS;
-}
+constexpr size_t NYM_ITEM_BYTES = 512;  // per signature beside its message: job, integers, prefix slot, alignment
 
 // decode s[a..b) on the pool; queue the device pass of the ones that reach the curve arithmetic
 int nym_chunk(ftz_idemix* ix, NymSlot& q, const ftz_owner_sig* s, size_t a, size_t b, int32_t* codes) {
   size_t n = b - a;
   std::vector<ftsh::NymDecoded> dec(n);
-  ix->pool->run((n + 63) / 64, [&](size_t p) {
-    for (size_t i = p * 64; i < n && i < (p + 1) * 64; i++)
-      ftsh::decode_owner_signature(s[a + i].owner, s[a + i].owner_len, s[a + i].sig, s[a + i].sig_len, dec[i],
+  par_for(ix->pool, n, [&](size_t i) {
+    ftsh::decode_owner_signature(s[a + i].owner, s[a + i].owner_len, s[a + i].sig, s[a + i].sig_len, dec[i],
                                  ix->curve);
   });
   std::vector<uint32_t> idx;  // chunk-relative
@@ -176,6 +157,7 @@ int nym_chunk(ftz_idemix* ix, NymSlot& q, const ftz_owner_sig* s, size_t a, size
                  [pool](size_t k, const std::function<void(size_t)>& f) { pool->run(k, f); }, ix->curve);
   const NymJob* jobs = reinterpret_cast<const NymJob*>(q.d_blob.p);
   QJDev* part = reinterpret_cast<QJDev*>(q.d_part.p);
+  sig_pass_begin(q, a, idx.data(), m);
   HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, L.total, hipMemcpyHostToDevice, q.st));
   const uint32_t gp = (uint32_t)((4 * m + 63) / 64), gf = (uint32_t)((m + 63) / 64);
   if (ix->curve == FTZ_CURVE_BN254) {
@@ -187,9 +169,7 @@ int nym_chunk(ftz_idemix* ix, NymSlot& q, const ftz_owner_sig* s, size_t a, size
   }
   HC(hipGetLastError());
   HC(hipMemcpyAsync(q.h_ok.p, q.d_ok.p, m, hipMemcpyDeviceToHost, q.st));
-  q.idx.resize(m);
-  for (size_t k = 0; k < m; k++) q.idx[k] = (uint32_t)(a + idx[k]);
-  q.busy = true;
+  q.enqueued = true;
   return FTZ_SUCCESS;
 }
 }  // namespace
@@ -199,31 +179,14 @@ extern "C" int ftz_verify_owner_signatures(ftz_idemix* ix, size_t n, const ftz_o
   for (size_t i = 0; i < n; i++) {
     if ((!s[i].owner && s[i].owner_len) || (!s[i].msg && s[i].msg_len) || (!s[i].sig && s[i].sig_len))
       return set_err(FTZ_E_INVALID, "null buffer with non-zero length");
-    if (s[i].msg_len > NYM_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
+    if (s[i].msg_len > ftsh::SIG_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
   }
   std::lock_guard<std::mutex> lk(ix->mu);
   HC(hipSetDevice(ix->ctx->device));
-  // chunks of <= NYM_CHUNK_SIGS signatures and < NYM_CHUNK_BYTES of blob, alternating
-  // between the two slots: chunk k+1 is decoded and laid out while chunk k runs
-  size_t a = 0, c = 0;
-  int rc = FTZ_SUCCESS;
-  while (a < n && rc == FTZ_SUCCESS) {
-    size_t b = a, bytes = 0;
-    while (b < n && b - a < NYM_CHUNK_SIGS && (b == a || bytes + s[b].msg_len + 512 < NYM_CHUNK_BYTES)) {
-      bytes += s[b].msg_len + 512;
-      b++;
-    }
-    NymSlot& q = ix->slot[c & 1];
-    rc = nym_collect(q, codes);
-    if (rc == FTZ_SUCCESS) rc = nym_chunk(ix, q, s, a, b, codes);
-    a = b;
-    c++;
-  }
-  for (NymSlot& q : ix->slot) {
-    int r2 = nym_collect(q, codes);
-    if (rc == FTZ_SUCCESS) rc = r2;
-  }
-  return rc;
+  return ftsh::sig_run(
+      n, ftsh::SIG_CHUNK_ITEMS, ftsh::SIG_CHUNK_BYTES, [&](size_t i) { return s[i].msg_len + NYM_ITEM_BYTES; },
+      [&](int k) { return sig_collect_verdicts(ix->slot[k], ix->slot[k].h_ok.p, codes); },
+      [&](int k, size_t a, size_t b) { return nym_chunk(ix, ix->slot[k], s, a, b, codes); });
 }
 
 // Auditor owner match: decode on the pool, one device pass over the tokens
@@ -236,10 +199,9 @@ extern "C" int ftz_audit_owners(ftz_idemix* ix, size_t n, const ftz_owner_audit*
   if (n > (1u << 26)) return set_err(FTZ_E_INVALID, "too many tokens in one call");
   if (ix->n_hattrs > 2 && !ix->heid_ok) return set_err(FTZ_E_PP, "issuer public key: HAttrs[2] not on the idemix curve");
   std::vector<ftsh::EidDecoded> dec(n);
-  ix->pool->run((n + 63) / 64, [&](size_t p) {
-    for (size_t i = p * 64; i < n && i < (p + 1) * 64; i++)
-      ftsh::decode_owner_audit(it[i].owner, it[i].owner_len, it[i].audit_info, it[i].audit_info_len, ix->n_hattrs,
-                               dec[i], ix->curve);
+  par_for(ix->pool, n, [&](size_t i) {
+    ftsh::decode_owner_audit(it[i].owner, it[i].owner_len, it[i].audit_info, it[i].audit_info_len, ix->n_hattrs,
+                             dec[i], ix->curve);
   });
   std::vector<uint32_t> idx;
   for (size_t i = 0; i < n; i++) {
@@ -297,26 +259,27 @@ int nymsign_check_handle(ftz_idemix* ix) {
 
 // wait for a slot's signing pass, write its protos and wipe the staged RNym values
 int nymsign_collect(ftz_idemix* ix, NymSlot& q, uint8_t* sigs, int32_t* codes) {
-  if (!q.sbusy) return FTZ_SUCCESS;
-  q.sbusy = false;
-  hipError_t he = hipStreamSynchronize(q.st);
-  explicit_bzero(q.h_blob.p + q.sec_at, q.sec_len);
-  if (he != hipSuccess)
-    return set_err(FTZ_E_DEVICE, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(he));
+  if (!q.busy) return FTZ_SUCCESS;
+  int rc = sig_pass_end(q);
   const size_t m = q.idx.size();
+  explicit_bzero(q.h_blob.p + q.rnym_at, m * 32);
+  if (rc != FTZ_SUCCESS) {  // the wipes the pass ends with may not have run
+    (void)hipMemset(q.d_blob.p + q.rnym_at, 0, m * 32);
+    (void)hipMemset(q.d_rand.p, 0, 3 * m * 32);
+    (void)hipMemset(q.d_part.p, 0, NYMSIGN_PARTS * m * sizeof(QJDev));
+    return rc;
+  }
   const uint8_t* raw = q.h_sig.p;
   const uint8_t* ok = q.h_sig.p + m * NYMSIGN_RAW_BYTES;
-  ix->pool->run((m + 63) / 64, [&](size_t p) {
-    for (size_t k = p * 64; k < m && k < (p + 1) * 64; k++) {
-      uint8_t* out = sigs + (size_t)q.idx[k] * FTZ_NYMSIG_LEN;
-      if (!ok[k]) {
-        memset(out, 0, FTZ_NYMSIG_LEN);
-        codes[q.idx[k]] = FTZ_ERR_SIGNATURE;
-        continue;
-      }
-      ftsh::encode_nym_signature(raw + k * NYMSIGN_RAW_BYTES, out);
-      codes[q.idx[k]] = FTZ_OK;
+  par_for(ix->pool, m, [&](size_t k) {
+    uint8_t* out = sigs + (size_t)q.idx[k] * FTZ_NYMSIG_LEN;
+    if (!ok[k]) {
+      memset(out, 0, FTZ_NYMSIG_LEN);
+      codes[q.idx[k]] = FTZ_ERR_SIGNATURE;
+      return;
     }
+    ftsh::encode_nym_signature(raw + k * NYMSIGN_RAW_BYTES, out);
+    codes[q.idx[k]] = FTZ_OK;
   });
   return FTZ_SUCCESS;
 }
@@ -326,9 +289,7 @@ int nymsign_chunk(ftz_idemix* ix, NymSlot& q, const ftz_nym_sign_item* it, size_
                   int32_t* codes) {
   const size_t n = b - a;
   std::vector<uint8_t> good(n, 0);
-  ix->pool->run((n + 63) / 64, [&](size_t p) {
-    for (size_t i = p * 64; i < n && i < (p + 1) * 64; i++) good[i] = ftsh::nymsign_nym_ok(it[a + i].nym) ? 1 : 0;
-  });
+  par_for(ix->pool, n, [&](size_t i) { good[i] = ftsh::nymsign_nym_ok(it[a + i].nym) ? 1 : 0; });
   std::vector<uint32_t> idx;  // chunk-relative
   for (size_t i = 0; i < n; i++) {
     if (good[i]) {
@@ -343,7 +304,6 @@ int nymsign_chunk(ftz_idemix* ix, NymSlot& q, const ftz_nym_sign_item* it, size_
   // blob: jobs | the RNym values, contiguous | 32 entropy bytes per hedged job | the prefix slots | every distinct
   // message (same pointer and length) once, aligned as nym_plan_layout aligns them
   std::vector<NymSignJob> jobs(m);
-  std::vector<uint8_t> copies(m, 0);
   size_t off = (m * sizeof(NymSignJob) + 15) & ~(size_t)15;
   const size_t rnym_at = off;
   off += m * 32;
@@ -356,24 +316,10 @@ int nymsign_chunk(ftz_idemix* ix, NymSlot& q, const ftz_nym_sign_item* it, size_
   }
   const size_t pre_at = off;
   off += m * NYM_PRE_SLOT;
-  std::map<std::pair<const uint8_t*, size_t>, uint32_t> at;
-  for (size_t k = 0; k < m; k++) {
-    const ftz_nym_sign_item& s = it[a + idx[k]];
-    jobs[k].msg_len = (uint32_t)s.msg_len;
-    jobs[k].signer = s.signer;
-    jobs[k].rnym = (uint32_t)(rnym_at + k * 32);
-    jobs[k].pre = (uint32_t)(pre_at + k * NYM_PRE_SLOT);
-    auto key = std::make_pair(s.msg, s.msg_len);
-    auto f = at.find(key);
-    if (f == at.end()) {
-      off = ((off + 15) & ~(size_t)15) + NymCurve<fp>::PRE % 16;
-      f = at.emplace(key, (uint32_t)off).first;
-      copies[k] = 1;
-      off += s.msg_len;
-    }
-    jobs[k].msg = f->second;
-  }
-  const size_t total = off + 64;  // slack: the hash reads whole 16-byte words
+  auto msg = [&](size_t k) { return std::make_pair(it[a + idx[k]].msg, it[a + idx[k]].msg_len); };
+  MsgLayout L;
+  sig_layout_messages(m, off, NymCurve<fp>::PRE % 16, msg, L);
+  const size_t total = L.end + 64;  // slack: the hash reads whole 16-byte words
   HC(q.h_blob.reserve(total));
   HC(q.d_blob.reserve(total));
   HC(q.h_sig.reserve(m * (NYMSIGN_RAW_BYTES + 1)));
@@ -381,31 +327,32 @@ int nymsign_chunk(ftz_idemix* ix, NymSlot& q, const ftz_nym_sign_item* it, size_
   HC(q.d_rand.reserve(3 * m * 32));
   HC(q.d_part.reserve(NYMSIGN_PARTS * m * sizeof(QJDev)));
   uint8_t* blob = q.h_blob.p;
-  memcpy(blob, jobs.data(), m * sizeof(NymSignJob));
-  ix->pool->run((m + 63) / 64, [&](size_t p) {
-    for (size_t k = p * 64; k < m && k < (p + 1) * 64; k++) {
-      const ftz_nym_sign_item& s = it[a + idx[k]];
-      memcpy(blob + jobs[k].rnym, s.r_nym, 32);
-      if (s.entropy) memcpy(blob + jobs[k].entropy, s.entropy, 32);
-      ftsh::nymsign_fill_prefix(blob + jobs[k].pre, s.nym, ix->ipk_hash, s.msg_len);
-      if (copies[k] && s.msg_len) memcpy(blob + jobs[k].msg, s.msg, s.msg_len);
-    }
-  });
   // from here on the staging buffer holds RNym values: nymsign_collect wipes them, also after an error below
-  q.sec_at = rnym_at;
-  q.sec_len = m * 32;
-  q.idx.resize(m);
-  for (size_t k = 0; k < m; k++) q.idx[k] = (uint32_t)(a + idx[k]);
-  q.sbusy = true;
+  q.rnym_at = rnym_at;
+  sig_pass_begin(q, a, idx.data(), m);
+  par_for(ix->pool, m + L.distinct.size(), [&](size_t k) {  // the jobs, then the messages
+    if (k >= m) return sig_copy_message(L, k - m, blob, msg);
+    const ftz_nym_sign_item& s = it[a + idx[k]];
+    NymSignJob& j = jobs[k];
+    j.msg = L.msg_off[k];
+    j.msg_len = (uint32_t)s.msg_len;
+    j.signer = s.signer;
+    j.rnym = (uint32_t)(rnym_at + k * 32);
+    j.pre = (uint32_t)(pre_at + k * NYM_PRE_SLOT);
+    memcpy(blob + k * sizeof(NymSignJob), &j, sizeof j);
+    memcpy(blob + j.rnym, s.r_nym, 32);
+    if (s.entropy) memcpy(blob + j.entropy, s.entropy, 32);
+    ftsh::nymsign_fill_prefix(blob + j.pre, s.nym, ix->ipk_hash, s.msg_len);
+  });
   const NymSignJob* djobs = reinterpret_cast<const NymSignJob*>(q.d_blob.p);
-  const uint32_t(*keys)[8] = reinterpret_cast<const uint32_t(*)[8]>(ix->skeys.p);
+  const uint32_t(*keys)[8] = ix->signers.keys();
   uint32_t(*d_rsk)[8] = reinterpret_cast<uint32_t(*)[8]>(q.d_rand.p);
   uint32_t(*d_rrn)[8] = d_rsk + m;
   uint32_t(*d_non)[8] = d_rrn + m;
   QJDev* part = reinterpret_cast<QJDev*>(q.d_part.p);
   uint8_t* d_raw = q.d_sig.p;
   uint8_t* d_ok = q.d_sig.p + m * NYMSIGN_RAW_BYTES;
-  HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, off, hipMemcpyHostToDevice, q.st));
+  HC(hipMemcpyAsync(q.d_blob.p, q.h_blob.p, L.end, hipMemcpyHostToDevice, q.st));
   HC(hipMemsetAsync(d_ok, 0, m, q.st));
   const uint32_t g1 = (uint32_t)((m + 63) / 64), gp = (uint32_t)((NYMSIGN_PARTS * m + 63) / 64);
   k_nymsign_pre<<<g1, 64, 0, q.st>>>(djobs, (uint32_t)m, q.d_blob.p, keys, d_rsk, d_rrn, d_non);
@@ -418,6 +365,7 @@ int nymsign_chunk(ftz_idemix* ix, NymSlot& q, const ftz_nym_sign_item* it, size_
   HC(hipMemsetAsync(q.d_blob.p + rnym_at, 0, m * 32, q.st));
   HC(hipMemsetAsync(q.d_rand.p, 0, 3 * m * 32, q.st));
   HC(hipMemsetAsync(q.d_part.p, 0, NYMSIGN_PARTS * m * sizeof(QJDev), q.st));
+  q.enqueued = true;
   return FTZ_SUCCESS;
 }
 }  // namespace
@@ -431,18 +379,10 @@ extern "C" int ftz_idemix_add_signer(ftz_idemix* ix, const uint8_t sk[32], int32
   be32_to_limbs(l, sk);
   std::lock_guard<std::mutex> lk(ix->mu);
   hipError_t he = hipSuccess;
-  if (ix->n_signers >= NYMSIGN_MAX_SIGNERS) {
+  if (ix->signers.n >= NYMSIGN_MAX_SIGNERS)
     rc = set_err(FTZ_E_INVALID, "too many signers (at most " + std::to_string(NYMSIGN_MAX_SIGNERS) + ")");
-  } else {
-    he = hipSetDevice(ix->ctx->device);
-    if (he == hipSuccess && !ix->skeys.p) {
-      he = ix->skeys.alloc((size_t)NYMSIGN_MAX_SIGNERS * 8);
-      if (he == hipSuccess) he = hipMemset(ix->skeys.p, 0, ix->skeys.n * sizeof(uint32_t));
-    }
-    // no pass is in flight (a call holds the mutex until it has collected its slots)
-    if (he == hipSuccess) he = hipMemcpy(ix->skeys.p + (size_t)ix->n_signers * 8, l, sizeof l, hipMemcpyHostToDevice);
-    if (he == hipSuccess) *signer = ix->n_signers++;
-  }
+  else
+    he = ix->signers.add(ix->ctx->device, NYMSIGN_MAX_SIGNERS, l, signer);
   explicit_bzero(l, sizeof l);
   if (he != hipSuccess) return set_err(FTZ_E_DEVICE, std::string("signer upload failed: ") + hipGetErrorString(he));
   return rc;
@@ -457,35 +397,18 @@ extern "C" int ftz_sign_owner_signatures(ftz_idemix* ix, size_t n, const ftz_nym
   for (size_t i = 0; i < n; i++) {
     if (!it[i].msg && it[i].msg_len) return set_err(FTZ_E_INVALID, "null buffer with non-zero length");
     if (!it[i].r_nym || !it[i].nym) return set_err(FTZ_E_INVALID, "null r_nym or nym");
-    if (it[i].msg_len > NYM_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
-    if (it[i].signer < 0 || it[i].signer >= ix->n_signers)
+    if (it[i].msg_len > ftsh::SIG_CHUNK_BYTES / 2) return set_err(FTZ_E_INVALID, "message larger than 512 MiB");
+    if (it[i].signer < 0 || it[i].signer >= ix->signers.n)
       return set_err(FTZ_E_INVALID, "signer " + std::to_string(it[i].signer) + " is not a registered signer");
     if (!ftsh::nymsign_scalar_ok(it[i].r_nym, false))
       return set_err(FTZ_E_INVALID, "r_nym of item " + std::to_string(i) + " is not below the group order");
   }
   if (n == 0) return FTZ_SUCCESS;
   HC(hipSetDevice(ix->ctx->device));
-  // chunks of <= NYM_CHUNK_SIGS signatures and < NYM_CHUNK_BYTES of blob, alternating
-  // between the two slots: chunk k+1 is laid out while chunk k runs
-  size_t a = 0, c = 0;
-  while (a < n && rc == FTZ_SUCCESS) {
-    size_t b = a, bytes = 0;
-    while (b < n && b - a < NYM_CHUNK_SIGS &&
-           (b == a || bytes + it[b].msg_len + NYMSIGN_ITEM_BYTES < NYM_CHUNK_BYTES)) {
-      bytes += it[b].msg_len + NYMSIGN_ITEM_BYTES;
-      b++;
-    }
-    NymSlot& q = ix->slot[c & 1];
-    rc = nymsign_collect(ix, q, sigs, codes);
-    if (rc == FTZ_SUCCESS) rc = nymsign_chunk(ix, q, it, a, b, sigs, codes);
-    a = b;
-    c++;
-  }
-  for (NymSlot& q : ix->slot) {
-    int r2 = nymsign_collect(ix, q, sigs, codes);
-    if (rc == FTZ_SUCCESS) rc = r2;
-  }
-  return rc;
+  return ftsh::sig_run(
+      n, ftsh::SIG_CHUNK_ITEMS, ftsh::SIG_CHUNK_BYTES, [&](size_t i) { return it[i].msg_len + NYMSIGN_ITEM_BYTES; },
+      [&](int k) { return nymsign_collect(ix, ix->slot[k], sigs, codes); },
+      [&](int k, size_t a, size_t b) { return nymsign_chunk(ix, ix->slot[k], it, a, b, sigs, codes); });
 }
 
 // MakeNym in batches: Nym_i = sk HSk + RNym_i HRand through the signing pass's parts kernel
@@ -494,7 +417,7 @@ extern "C" int ftz_idemix_make_nyms(ftz_idemix* ix, int32_t signer, size_t n, co
   int rc = nymsign_check_handle(ix);
   if (rc != FTZ_SUCCESS) return rc;
   std::lock_guard<std::mutex> lk(ix->mu);
-  if (signer < 0 || signer >= ix->n_signers)
+  if (signer < 0 || signer >= ix->signers.n)
     return set_err(FTZ_E_INVALID, "signer " + std::to_string(signer) + " is not a registered signer");
   for (size_t i = 0; i < n; i++)
     if (!ftsh::nymsign_scalar_ok(r_nyms + i * 32, false))
@@ -502,8 +425,8 @@ extern "C" int ftz_idemix_make_nyms(ftz_idemix* ix, int32_t signer, size_t n, co
   if (n == 0) return FTZ_SUCCESS;
   HC(hipSetDevice(ix->ctx->device));
   NymSlot& q = ix->slot[0];
-  const uint32_t(*keys)[8] = reinterpret_cast<const uint32_t(*)[8]>(ix->skeys.p);
-  const size_t cap = NYM_CHUNK_SIGS;
+  const uint32_t(*keys)[8] = ix->signers.keys();
+  const size_t cap = ftsh::SIG_CHUNK_ITEMS;
   HC(ix->h_mk.reserve(cap * 64));
   HC(ix->d_mk.reserve(cap * (32 + 64)));
   HC(q.d_rand.reserve(3 * cap * 32));

@@ -11,7 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHUNK_SIGS = 4096  # ecdsa_rt.hip ECDSA_CHUNK_SIGS
+CHUNK_SIGS = 4096  # host/sigpipe.h SIG_CHUNK_ITEMS
 KEYS_PER_HANDLE = 4
 
 
@@ -73,10 +73,11 @@ def test_every_case_on_both_routes(fx):
     assert "doubling" in accepted and "s_half_n" in accepted and len(accepted) >= 30
 
 
-@pytest.mark.parametrize("size", [1, 63, 64, 65, CHUNK_SIGS + 1])
+@pytest.mark.parametrize("size", [1, 63, 64, 65, CHUNK_SIGS + 1, 2 * CHUNK_SIGS + 1])
 def test_tiled_batches_mixed_routes(fx, size):
     """valid and invalid cases interleaved, registered and ad-hoc items and all
-    message lengths mixed within the waves; every position's code matches"""
+    message lengths mixed within the waves; every position's code matches.  The
+    last size is three chunks: the third goes into the slot the first one used"""
     h = fx["handles"][0]
     for start in ((0, 17) if size < 1000 else (5,)):
         items, want = [], []

@@ -17,7 +17,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHUNK_SIGS = 4096  # ecdsa_rt.hip ECDSA_CHUNK_SIGS
+CHUNK_SIGS = 4096  # host/sigpipe.h SIG_CHUNK_ITEMS
 RFC_X = 0xC9AFA9D845BA75166B5C215767B1D6934E50C3DB36E89B127B8A622B120F6721
 RFC_U = ("60FED4BA255A9D31C961EB74C6356D68C049B8923B61FA6CE669622E60F29FB6"
          "7903FE1008B8BC99A41AE9E95628BC64F2F1B20C2D7E9F5177A3C294D4462299")
@@ -86,11 +86,12 @@ def test_every_fixture_case_byte_exact(fx):
     assert len(seen) == len(g["cases"]) >= 40
 
 
-@pytest.mark.parametrize("size", [1, 63, 64, 65, CHUNK_SIGS + 1])
+@pytest.mark.parametrize("size", [1, 63, 64, 65, CHUNK_SIGS + 1, 2 * CHUNK_SIGS + 1])
 def test_batches_sign_then_verify(fx, size):
     """signers, message lengths and entropy / no entropy mixed inside the first wave; every position
     byte-equal to the reference; the same handle accepts every signature by registered key and ad hoc,
-    and refuses each one over its neighbour's message"""
+    and refuses each one over its neighbour's message.  The last size is three chunks: the third goes
+    into the slot the first one used"""
     h, pool = fx["handles"][0], fx["pool"]
     for start in ((0, 23) if size < 1000 else (3,)):
         pick = [pool[(start + i) % POOL] for i in range(size)]

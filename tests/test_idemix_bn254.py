@@ -286,6 +286,19 @@ def test_gpu_bn254_batch_and_tamper(gold, ipk, gpu_bn):
 
 
 @pytest.mark.gpu
+def test_gpu_bn254_three_chunks_reuse_a_slot(gold, gpu_bn):
+    """2 * 4096 + 1 signatures (golden cases tiled from an offset) are three chunks (host/sigpipe.h
+    SIG_CHUNK_ITEMS): the third goes into the slot the first one used; every position's code"""
+    cs = gold["cases"]
+    its = items(cs)
+    sel = [(k + 3) % len(cs) for k in range(2 * 4096 + 1)]
+    want = [cs[k]["expect"] for k in sel]
+    assert len(set(want[:64])) >= 2 and len(set(want[-64:])) >= 2
+    got = gpu_bn.verify_owner_signatures([its[k] for k in sel])
+    assert got == want, [i for i in range(len(sel)) if got[i] != want[i]][:10]
+
+
+@pytest.mark.gpu
 def test_gpu_bn254_audit_owners(gold, gpu_bn):
     cs = gold["audit_cases"]
     its = audit_items(cs)

@@ -20,7 +20,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHUNK_SIGS = 4096  # idemix_rt.hip NYM_CHUNK_SIGS
+CHUNK_SIGS = 4096  # host/sigpipe.h SIG_CHUNK_ITEMS
 FTZ_ERR_OWNER, FTZ_ERR_SIGNATURE = 9, 10
 POOL = 64
 
@@ -90,11 +90,12 @@ def test_every_fixture_case_byte_exact(fx):
     assert ix.verify_owner_signatures([(o, it[3], s) for o, it, s in zip(owners, items, sigs)]) == [0] * len(cases)
 
 
-@pytest.mark.parametrize("size", [1, 63, 64, 65, CHUNK_SIGS + 1])
+@pytest.mark.parametrize("size", [1, 63, 64, 65, CHUNK_SIGS + 1, 2 * CHUNK_SIGS + 1])
 def test_batches_sign_then_verify(fx, size):
     """signers, pseudonyms, message lengths and entropy / no entropy mixed inside the first wave; every
     position byte-equal to the reference; the same handle accepts every signature, and refuses one
-    over a message with one flipped byte"""
+    over a message with one flipped byte.  The last size is three chunks: the third goes into the
+    slot the first one used"""
     ix, pool = fx["ix"], fx["pool"]
     for start in ((0, 23) if size < 1000 else (3,)):
         pick = [pool[(start + i) % POOL] for i in range(size)]
