@@ -25,6 +25,10 @@
 // reduction and a final canonical subtraction (f29_to_fp), so the G1 code around
 // the loops keeps its fp types.  tests/native/emu_exec.cpp checks every
 // formula against the fp.h ones.
+//
+// The G1 doubling and mixed additions (j29_dbl, j29_madd, x29_madd) run on the
+// balanced scanned products further down (s29_*): one reduction per sum of
+// products, no sweeps; tests/native/g1fused_main.cpp checks them.
 #pragma once
 #include "curve.h"
 #include "fp.h"
@@ -454,60 +458,170 @@ FTS_HD f29 f29_breduce(const f29& a) { return f29_lin2(a, 1, a, 0); }
 FTS_HD q2 q2_from_fp2(const fp2& a) { return {f29_breduce(f29_from_fp(a.c0)), f29_breduce(f29_from_fp(a.c1))}; }
 FTS_HD fp2 q2_to_fp2(const q2& a) { return {f29_to_fp(a.c0), f29_to_fp(a.c1)}; }
 
+// ------------------------------------- balanced products, scanned (one row)
+// The single-row counterpart of dev/g2x29.h scan2_step, for the G1 formulas
+// below: (a b [+ c d]) / R [+ f] with ONE Montgomery reduction, by product
+// scanning -- column k of the product(s) joins one running sum, the multiples
+// m_i p_j (i + j = k) of the balanced digits already chosen are added, and the
+// sum yields the next digit m_k (k < 9: it then divides exactly by 2^29) or the
+// next balanced output limb (k >= 9, where f's limb k - 9 joins first: R f, as
+// in w29_redc_t<true>).  One accumulator and nine digits are live instead of
+// 17 columns.  A square takes its cross products once against a doubled
+// operand (45 limb products); with e = -x it is the row of -x^2.
+//
+// Bounds (L = max |limb| in units of 2^28, limb 8 included; B = |value| in
+// units of p; R = 2^261 > 169 p):
+//   column: at most 9 limb products per product row, each <= L_a L_b 2^56, the
+//     9 multiples m_i p_j <= 2^56 each and the carry of the column before
+//     (< 2^35): |sum| < (9 (L_a L_b + L_c L_d + 1) + 1) 2^56 < 2^63 needs
+//     L_a L_b + L_c L_d <= 13 (a square counts L_x^2: its doubled limbs
+//     2 L_x 2^28 <= 2^31 need L_x <= 7);
+//   f adds at most 3 x 2^28 to a column: nothing against 2^56;
+//   value: |m p / R| <= (1/2 + 2^-29) p, so
+//     B_out <= (B_a B_b + B_c B_d) / 169 + 0.5001 + B_f;
+//   limbs 0..7 of the result are balanced digits in [-2^28, 2^28), limb 8 is
+//     the signed rest: |limb 8| <= B_out p / 2^232 + 1 < B_out 2^21.7 + 1.
+// A result with B_out < 1 that is a multiple of p is 0, and 0 has one balanced
+// representation (all limbs 0): f29_reduced_zero tests it.
+enum { S29_NONE = 0, S29_MUL = 1, S29_SQR = 2 };
+
+template <int KIND>
+FTS_HD void s29_col(int64_t& acc, const f29& a, const f29& b, const f29& b2, int k) {
+  if (KIND == S29_MUL) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      const int j = k - i;
+      if (j < 0 || j > 8) continue;
+      acc += (int64_t)a.l[i] * b.l[j];
+    }
+  } else if (KIND == S29_SQR) {  // b = +-a, b2 = 2 b
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      const int j = k - i;
+      if (j <= i || j > 8) continue;
+      acc += (int64_t)b2.l[i] * a.l[j];
+    }
+    if ((k & 1) == 0) acc += (int64_t)b.l[k / 2] * a.l[k / 2];
+  }
+}
+
+// (row1 + row2) / R + f; a row of kind S29_MUL is a b (c d), of kind S29_SQR
+// b a with b = +-a (d c with d = +-c)
+template <int K1, int K2, bool ADD>
+FTS_HD f29 s29_scan(const f29& a, const f29& b, const f29& c, const f29& d, const f29& f) {
+  FTS_COUNT_MAD(64 * ((K1 != S29_NONE) + (K2 != S29_NONE)) + 72);  // the 32-bit equivalent, for opcounts
+  const f29 b2 = K1 == S29_SQR ? f29_add(b, b) : b, d2 = K2 == S29_SQR ? f29_add(d, d) : d;
+  int64_t acc = 0;
+  int32_t m[9];
+  f29 r;
+#pragma unroll
+  for (int k = 0; k < 17; k++) {
+    s29_col<K1>(acc, a, b, b2, k);
+    s29_col<K2>(acc, c, d, d2, k);
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      const int j = k - i;
+      if (i >= k || j < 0 || j > 8) continue;
+      acc += (int64_t)m[i] * P29B[j];
+    }
+    if (k < 9) {
+      const uint32_t m0 = ((uint32_t)acc * P29_INV) & (uint32_t)F29_MASK;
+      m[k] = (int32_t)((m0 + (uint32_t)F29_HALF) & (uint32_t)F29_MASK) - F29_HALF;
+      acc = (acc + (int64_t)m[k] * P29B[0]) >> 29;  // a multiple of 2^29 now
+    } else {
+      if (ADD) acc += f.l[k - 9];
+      r.l[k - 9] = f29_bdigit(acc);
+      acc = (acc + F29_HALF) >> 29;
+    }
+  }
+  r.l[8] = (int32_t)acc + (ADD ? f.l[8] : 0);
+  return r;
+}
+
+FTS_HD f29 s29_mul(const f29& a, const f29& b) { return s29_scan<S29_MUL, S29_NONE, false>(a, b, a, a, a); }
+FTS_HD f29 s29_sqr(const f29& a) { return s29_scan<S29_SQR, S29_NONE, false>(a, a, a, a, a); }
+// a^2 / R + f
+FTS_HD f29 s29_sqr_add(const f29& a, const f29& f) { return s29_scan<S29_SQR, S29_NONE, true>(a, a, a, a, f); }
+// (a b + c d) / R
+FTS_HD f29 s29_mul2(const f29& a, const f29& b, const f29& c, const f29& d) {
+  return s29_scan<S29_MUL, S29_MUL, false>(a, b, c, d, a);
+}
+// (a b - c^2) / R
+FTS_HD f29 s29_mul_sub_sqr(const f29& a, const f29& b, const f29& c) {
+  return s29_scan<S29_MUL, S29_SQR, false>(a, b, c, f29_neg(c), a);
+}
+
+// 3 a / 2 mod p for balanced a, without a sweep: v = 3 a + (p when a is odd) is
+// even -- p is odd and every limb above the lowest weighs a multiple of 2, so
+// the parity of a value is limb 0's -- and
+//   v / 2 = sum_i ((v_i >> 1) + (v_{i+1} & 1) 2^28) 2^(29 i)
+// (an odd v_i leaves 2^(29 i - 1), which is 2^28 in limb i - 1; v_0 is even).
+// |v_i| <= 3 x 2^28 + 2^28, so |limb| <= 2^29 + 2^28 (L = 3: a multiplicand
+// only) and |value| <= (3 |a| + p) / 2.
+FTS_HD f29 f29_half3(const f29& a) {
+  const int32_t odd = -(a.l[0] & 1);
+  int32_t v[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) v[i] = 3 * a.l[i] + (odd & P29B[i]);
+  f29 r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.l[i] = (v[i] >> 1) + ((v[i + 1] & 1) << 28);
+  r.l[8] = v[8] >> 1;
+  return r;
+}
+
 // ---------------------------------------------------------------- G1 (a = 0)
-// Jacobian point in this form with an explicit infinity flag.  Coordinates
-// between operations: normalised, |value| <= 3p/2 (f29_reduce outputs or
-// products).  Same formulas (and so the same projective point up to the
-// representation of each coordinate) as curve.h jac_dbl / jac_add_aff.
+// Jacobian point in this form with an explicit infinity flag.  j29_dbl and
+// j29_madd take coordinates with |limb| <= 2^29 (L <= 2) and |value| <= 2.5 p
+// (their own outputs, f29_reduce outputs and the products of the first form)
+// and return balanced ones (L = 1) with |X3| <= 2.1 p, |Y3|, |Z3| <= 0.56 p.
+// They return the same projective point as curve.h jac_dbl / jac_add_aff in
+// another scaling (lambda = 1/2 of their (X : Y : Z)), so every affine result
+// is the same.
 struct j29 {
   f29 x, y, z;
   bool inf;
 };
 
-// dbl-2009-l: 2M + 5S.  Bounds in comments as (B, L).
+// dbl-2009-l's point scaled by lambda = 1/2 (X3 / 4, Y3 / 8, Z3 / 2), which
+// needs no factor above 2 inside a product sum: with T = Y^2, S = X T and the
+// halved slope M = 3 X^2 / 2,
+//   X3 = M^2 - 2 S,  Y3 = M (S - X3) - T^2,  Z3 = Y Z:
+// 2M + 4S in six reductions, no sweep and no quotient.  (B, L) in comments,
+// for inputs (2.5, 2).
 FTS_HD j29 j29_dbl(const j29& p) {
-  f29 A = f29_sqr(p.x);                            // (2, 1)
-  f29 Bq = f29_sqr(p.y);                           // (2, 1)
-  f29 C = f29_sqr(Bq);                             // (2, 1)
-  f29 T2 = f29_sqr(f29_norm(f29_add(p.x, Bq)));    // (1.5 + 2)^2 < 169
-  f29 D1 = f29_norm(f29_sub(f29_sub(T2, A), C));   // (6, 1)
-  f29 D = f29_add(D1, D1);                         // (12, 2)
-  f29 E = f29_norm(f29_add(f29_add(A, A), A));     // (6, 1)
-  f29 F = f29_sqr(E);                              // 36: (2, 1)
-  f29 X3 = f29_reduce(f29_sub(f29_norm(f29_sub(F, D)), D));        // (26, 3) -> (1.5, 1)
-  f29 Y3a = f29_mul(E, f29_norm(f29_sub(D, X3)));  // 6 x 13.5 < 169: (2, 1)
-  f29 C2 = f29_add(C, C);
-  f29 C4 = f29_norm(f29_add(C2, C2));              // (8, 1)
-  f29 Y3 = f29_reduce(f29_sub(Y3a, f29_add(C4, C4)));              // (18, 3) -> (1.5, 1)
-  f29 Z3 = f29_mul(f29_add(p.y, p.y), p.z);        // 3 x 2, L 2 x 1: (2, 1); infinity keeps z = 0
+  const f29 T = s29_sqr(p.y);                              // 6.25 / 169 + 0.5: (0.54, 1)
+  const f29 Z3 = s29_mul(p.y, p.z);                        // (0.54, 1), column 4 + 1; infinity keeps its flag
+  const f29 S = s29_mul(p.x, T);                           // (0.51, 1)
+  const f29 M = f29_half3(s29_sqr(p.x));                   // (3 x 0.54 + 1) / 2: (1.31, 3)
+  const f29 X3 = s29_sqr_add(M, f29_neg(f29_add(S, S)));   // 0.02 + 0.5 + 1.02: (1.54, 1), column 9 + 1
+  const f29 Y3 = s29_mul_sub_sqr(M, f29_sub(S, X3), T);    // (1.31 x 2.05 + 0.3) / 169 + 0.5: (0.52, 1), column 6 + 1 + 1
   return {X3, Y3, Z3, p.inf};
 }
 
-// add-2007-bl mixed addition p + (x2, y2), (x2, y2) affine and not infinity,
-// B <= 32, L <= 1 (f29_from_fp outputs): 7M + 4S.  The exceptional cases are
-// caught after the fact: Z3 = 2 Z1 H vanishes iff H does, and then the sum is
-// infinity (rr != 0) or a doubling (rr == 0, p == (x2, y2)).
+// Mixed addition p + (x2, y2), (x2, y2) affine and not infinity, B <= 32 and
+// |limb| < 2^29 (f29_from_fp outputs, possibly negated, or products): the
+// point of madd-2007-bl scaled by lambda = 1/2,
+//   H = x2 Z1^2 - X1,  r = y2 Z1^3 - Y1,  V = X1 H^2,
+//   X3 = r^2 - H^3 - 2 V,  Y3 = r (V - X3) - Y1 H^3,  Z3 = Z1 H:
+// 8M + 3S in ten reductions.  The exceptional cases are caught after the fact:
+// Z3 = Z1 H (|Z3| < p) vanishes iff H does, and then the sum is infinity
+// (r != 0) or a doubling (r == 0, p == (x2, y2)).
 FTS_HD j29 j29_madd(const j29& p, const f29& x2, const f29& y2) {
-  if (p.inf) return {f29_reduce(x2), f29_reduce(y2), f29_reduce(f29_from_fp(fe_one<ModP>())), false};
-  f29 Z1Z1 = f29_sqr(p.z);                         // (2, 1)
-  f29 U2 = f29_mul(x2, Z1Z1);                      // 32 x 2: (2, 1)
-  f29 S2 = f29_mul(y2, f29_mul(p.z, Z1Z1));        // (2, 1)
-  f29 H = f29_norm(f29_sub(U2, p.x));              // (3.5, 1)
-  f29 rr = f29_sub(S2, p.y);                       // (3.5, 2)
-  f29 HH = f29_sqr(H);                             // (2, 1)
-  f29 HH2 = f29_add(HH, HH);
-  f29 I = f29_norm(f29_add(HH2, HH2));             // (8, 1)
-  f29 J = f29_mul(H, I);                           // 28: (2, 1)
-  f29 r2 = f29_norm(f29_add(rr, rr));              // (7, 1)
-  f29 V = f29_mul(p.x, I);                         // 12: (2, 1)
-  f29 X3 = f29_reduce(f29_sub(f29_sub(f29_sub(f29_sqr(r2), J), V), V));  // (8, 4) -> (1.5, 1)
-  f29 Y3a = f29_mul(r2, f29_norm(f29_sub(V, X3))); // 7 x 3.5: (2, 1)
-  f29 YJ = f29_mul(p.y, J);                        // (2, 1)
-  f29 Y3 = f29_reduce(f29_sub(f29_sub(Y3a, YJ), YJ));              // (6, 3) -> (1.5, 1)
-  f29 ZH = f29_norm(f29_add(p.z, H));              // (5, 1)
-  f29 Z3 = f29_reduce(f29_sub(f29_sub(f29_sqr(ZH), Z1Z1), HH));    // 25: (6, 3) -> (1.5, 1)
+  if (p.inf) return {f29_breduce(x2), f29_breduce(y2), f29_breduce(f29_from_fp(fe_one<ModP>())), false};
+  const f29 Z1Z1 = s29_sqr(p.z);                           // (0.54, 1)
+  const f29 U2 = s29_mul(x2, Z1Z1);                        // 32 x 0.54 / 169 + 0.5: (0.61, 1)
+  const f29 S2 = s29_mul(y2, s29_mul(p.z, Z1Z1));          // (0.61, 1)
+  const f29 H = f29_sub(U2, p.x);                          // (3.11, 3)
+  const f29 Z3 = s29_mul(p.z, H);                          // 7.8 / 169 + 0.5: (0.55, 1), column 6 + 1
+  const f29 rr = f29_sub(S2, p.y);                         // (3.11, 3)
+  const f29 HH = s29_sqr(H);                               // (0.56, 1), column 9 + 1
+  const f29 HHH = s29_mul(H, HH);                          // (0.52, 1)
+  const f29 V = s29_mul(p.x, HH);                          // (0.51, 1)
+  const f29 X3 = s29_sqr_add(rr, f29_neg(f29_add(HHH, f29_add(V, V))));  // 0.06 + 0.5 + 0.52 + 1.02: (2.1, 1)
+  const f29 Y3 = s29_mul2(rr, f29_sub(V, X3), f29_neg(p.y), HHH);        // (3.11 x 2.61 + 1.3) / 169 + 0.5: (0.56, 1), column 6 + 2 + 1
   if (f29_reduced_zero(Z3)) {
-    if (f29_is_zero(rr)) return j29_dbl(p);  // p == (x2, y2)
+    if (f29_reduced_zero(f29_breduce(rr))) return j29_dbl(p);  // p == (x2, y2)
     j29 o = p;
     o.inf = true;
     return o;
@@ -556,7 +670,8 @@ FTS_HD j29 j29_add(const j29& p, const j29& q) {
 // x = X / ZZ, y = Y / ZZZ with ZZ^3 = ZZZ^2: the mixed addition needs 8M + 2S
 // (madd-2008-s) against 7M + 4S and the doublings of the Jacobian one -- the
 // MSM bucket sums are long runs of mixed additions.  Coordinates between
-// operations as j29's: normalised, |value| <= 2p.
+// operations: x29_madd's balanced outputs or the first form's normalised ones,
+// |value| <= 2.5 p.
 struct x29 {
   f29 x, y, zz, zzz;
   bool inf;
@@ -579,7 +694,52 @@ FTS_HD x29 x29_dbl_aff(const f29& x0, const f29& y0) {
 // p + (x2, y2), (x2, y2) affine and not infinity, B <= 32, L <= 1 (f29_from_fp
 // outputs, possibly negated): madd-2008-s.  P = U2 - X1 vanishes iff the x
 // coordinates agree: then the sum is a doubling (R = 0) or infinity.
+// In the scanned balanced products (s29_*, above): accumulator coordinates
+// with |limb| <= 2^29 and |value| <= 2.5 p in (x29_dbl_aff's, the first form's
+// products), balanced ones out with |X3| <= 2.1 p and the rest <= 0.56 p; nine
+// reductions.  ZZ3 = ZZ PP (|ZZ3| < p) vanishes iff P does.
 FTS_HD x29 x29_madd(const x29& p, const f29& x2, const f29& y2) {
+  if (p.inf) {
+    const f29 one = f29_breduce(f29_from_fp(fe_one<ModP>()));
+    return {f29_breduce(x2), f29_breduce(y2), one, one, false};
+  }
+  const f29 U2 = s29_mul(x2, p.zz);                        // 32 x 2.5 / 169 + 0.5: (0.98, 1)
+  const f29 S2 = s29_mul(y2, p.zzz);                       // (0.98, 1)
+  const f29 P = f29_sub(U2, p.x);                          // (3.5, 3)
+  const f29 R = f29_sub(S2, p.y);                          // (3.5, 3)
+  const f29 PP = s29_sqr(P);                               // (0.58, 1), column 9 + 1
+  const f29 ZZ3 = s29_mul(p.zz, PP);                       // (0.51, 1)
+  // the compiler tests ZZ3 here whatever the source order, and the operands that
+  // cross that branch would be multiplied as sign-extended 64-bit copies (pin32)
+  f29 Pq = P, PPq = PP, Rq = R, X1 = p.x, nY1 = f29_neg(p.y), ZZZ1 = p.zzz;
+  pin29(Pq);
+  pin29(PPq);
+  pin29(Rq);
+  pin29(X1);
+  pin29(nY1);
+  pin29(ZZZ1);
+  const f29 PPP = s29_mul(Pq, PPq);                        // (0.52, 1)
+  const f29 ZZZ3 = s29_mul(ZZZ1, PPP);                     // (0.51, 1)
+  const f29 Q = s29_mul(X1, PPq);                          // (0.51, 1)
+  const f29 X3 = s29_sqr_add(Rq, f29_neg(f29_add(PPP, f29_add(Q, Q))));  // 0.08 + 0.5 + 0.52 + 1.02: (2.1, 1)
+  const f29 Y3 = s29_mul2(Rq, f29_sub(Q, X3), nY1, PPP);                 // (3.5 x 2.61 + 1.3) / 169 + 0.5: (0.57, 1)
+  // after the fact, as j29_madd
+  if (f29_reduced_zero(ZZ3)) {
+    if (f29_reduced_zero(f29_breduce(Rq))) return x29_dbl_aff(x2, y2);
+    x29 o = p;
+    o.inf = true;
+    return o;
+  }
+  return {X3, Y3, ZZ3, ZZZ3, false};
+}
+
+// The same sum in the first form with column-sum products (f29_mul_c /
+// f29_sqr_c: 17 independent accumulators, short dependent chains), for the
+// MSM's bucket sums (dev/msm.h), where it stays: both fused forms issue 2 %
+// fewer instructions there and run 1-2 % longer (profiles/r10/msm_madd_ab.txt).
+// p's coordinates normalised or balanced with |value| <= 2 p; (x2, y2) as
+// x29_madd's, L <= 1.  P = U2 - X1 vanishes iff the x coordinates agree.
+FTS_HD x29 x29_madd_c(const x29& p, const f29& x2, const f29& y2) {
   if (p.inf) {
     f29 one = f29_reduce(f29_from_fp(fe_one<ModP>()));
     return {f29_reduce(x2), f29_reduce(y2), one, one, false};

@@ -632,11 +632,20 @@ FTS_HD g1j g1_mul_glv16(const g1a& p, const uint32_t k[8], G1Dev* tb, size_t st)
   if (p.inf) return jac_inf<fp>();
   return g1_mul_glv16_iso(p, fe_one<ModP>(), k, tb, st);
 }
+// The window loop on given halves: (-1)^n1 k1 V + (-1)^n2 k2 phi(V) for any
+// k1, k2 < 2^128 (glv_split's stay below 2^127, so a test that wants the top
+// window's digit or a chosen digit pattern calls this).
+FTS_HD g1j g1_mul_glv16_halves(const g1a& p, const fp& zin, const uint32_t k1[4], bool n1, const uint32_t k2[4],
+                               bool n2, G1Dev* tb, size_t st);
 FTS_HD g1j g1_mul_glv16_iso(const g1a& p, const fp& zin, const uint32_t k[8], G1Dev* tb, size_t st) {
-  g1j acc = jac_inf<fp>();
   uint32_t k1[4], k2[4];
   bool n1, n2;
   glv_split(k, k1, n1, k2, n2);
+  return g1_mul_glv16_halves(p, zin, k1, n1, k2, n2, tb, st);
+}
+FTS_HD g1j g1_mul_glv16_halves(const g1a& p, const fp& zin, const uint32_t k1[4], bool n1, const uint32_t k2[4],
+                               bool n2, G1Dev* tb, size_t st) {
+  g1j acc = jac_inf<fp>();
   g1a P1 = n1 ? aff_neg(p) : p;
   g1j T = jac_from_aff(P1);
   fp pre = fe_one<ModP>();
@@ -680,7 +689,7 @@ FTS_HD g1j g1_mul_glv16_iso(const g1a& p, const fp& zin, const uint32_t k[8], G1
     j29 na = j29_madd(a, f29_from_fp(x1), (d1 < 0) ? f29_neg(Y) : Y);
     if (m1) a = na;
     Y = f29_from_fp(y2);
-    na = j29_madd(a, f29_mul(f29_from_fp(x2), beta29), ((d2 < 0) != flip) ? f29_neg(Y) : Y);
+    na = j29_madd(a, s29_mul(f29_from_fp(x2), beta29), ((d2 < 0) != flip) ? f29_neg(Y) : Y);
     if (m2) a = na;
   }
   acc = j29_to(a);

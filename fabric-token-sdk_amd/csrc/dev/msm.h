@@ -334,7 +334,7 @@ FTS_HD g1j msm_job_slot(const MsmPlan& p, uint32_t j, const uint32_t* owner, con
     g1a P = g1_load(cur);
     if (!P.inf) {
       f29 Y = f29_from_fp(P.y);
-      a = x29_madd(a, f29_from_fp(P.x), sign ? f29_neg(Y) : Y);
+      a = x29_madd_c(a, f29_from_fp(P.x), sign ? f29_neg(Y) : Y);
     }
   }
   return j29_to(x29_to_j29(a));

@@ -19,6 +19,13 @@ __global__ void __launch_bounds__(256) k_devcheck(uint32_t n, const uint32_t* in
   dc_apply<OP>(in + (size_t)j * NIN, out + (size_t)j * NOUT);
 }
 
+template <int OP, uint32_t NIN, uint32_t NOUT>
+__global__ void __launch_bounds__(256) k_devcheck_g1(uint32_t n, const uint32_t* in, uint32_t* out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  dc_g1_apply<OP>(in + (size_t)j * NIN, out + (size_t)j * NOUT);
+}
+
 __global__ void __launch_bounds__(256) k_devcheck_sha(uint32_t n, const uint8_t* arena, const uint32_t* first,
                                                       const uint32_t* segs, uint32_t* out) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,6 +68,44 @@ extern "C" int ftz_devcheck(int device, int op, uint32_t n, uint32_t block, cons
     k_devcheck<DC_##name, nin, nout><<<blocks, block>>>(n, din, dout); \
     break;
       DC_OPS(DC_X)
+#undef DC_X
+    }
+    if ((e = hipGetLastError()) == hipSuccess && (e = hipDeviceSynchronize()) == hipSuccess)
+      e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  return -(int)e;
+}
+
+// The G1 table (DC_G1_OPS), as ftz_devcheck_info / ftz_devcheck are for DC_OPS
+extern "C" int ftz_devcheck_g1_info(int op, char name[32], uint32_t* nin, uint32_t* nout) {
+  if (op >= 0 && op < DC_G1_OP_COUNT) {
+    const DcInfo& e = dc_g1_table()[op];
+    strncpy(name, e.name, 31);
+    name[31] = 0;
+    *nin = e.nin;
+    *nout = e.nout;
+  }
+  return DC_G1_OP_COUNT;
+}
+extern "C" int ftz_devcheck_g1(int device, int op, uint32_t n, uint32_t block, const uint32_t* in, uint32_t* out) {
+  if (op < 0 || op >= DC_G1_OP_COUNT || n == 0 || (block != 64 && block != 256) || !in || !out) return -1000;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return -(int)e;
+  const DcInfo& info = dc_g1_table()[op];
+  const uint32_t blocks = (n + block - 1) / block;
+  const size_t in_bytes = (size_t)n * info.nin * 4, out_bytes = (size_t)blocks * block * info.nout * 4;
+  uint32_t *din = nullptr, *dout = nullptr;
+  if ((e = hipMalloc(&din, in_bytes)) == hipSuccess && (e = hipMalloc(&dout, out_bytes)) == hipSuccess &&
+      (e = hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemset(dout, DC_SENTINEL & 0xFF, out_bytes)) == hipSuccess) {
+    switch (op) {
+#define DC_X(name, nin, nout)                                              \
+  case DC_##name:                                                          \
+    k_devcheck_g1<DC_##name, nin, nout><<<blocks, block>>>(n, din, dout); \
+    break;
+      DC_G1_OPS(DC_X)
 #undef DC_X
     }
     if ((e = hipGetLastError()) == hipSuccess && (e = hipDeviceSynchronize()) == hipSuccess)

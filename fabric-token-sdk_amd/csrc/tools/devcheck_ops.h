@@ -257,6 +257,54 @@ FTS_HD void dc_apply(const uint32_t* in, uint32_t* out) {
   }
 }
 
+// ---- the fused G1 formulas of dev/fp29.h against the 32-bit ones of
+// dev/curve.h (tests/test_gpu_g1_fused.py), a table of its own beside DC_OPS:
+// an op reads an accumulator in raw 29-bit limbs (j29: X Y Z, x29: X Y ZZ ZZZ),
+// its infinity flag and, for the additions, an affine operand (x2 y2 in
+// limbs); it writes the new routine's result as a 32-bit Jacobian point (24
+// words) and then the 32-bit formula's on the same operands (24 words).  The
+// two are the same projective point in different scalings.
+#define DC_G1_OPS(X) X(g1f_dbl, 28, 48) X(g1f_madd, 46, 48) X(g1f_xmadd, 55, 48)
+
+enum DcG1Op : int {
+#define DC_X(name, nin, nout) DC_##name,
+  DC_G1_OPS(DC_X)
+#undef DC_X
+  DC_G1_OP_COUNT
+};
+inline const DcInfo* dc_g1_table() {
+  static const DcInfo t[DC_G1_OP_COUNT] = {
+#define DC_X(name, nin, nout) {#name, nin, nout},
+      DC_G1_OPS(DC_X)
+#undef DC_X
+  };
+  return t;
+}
+FTS_HD void dc_stj(uint32_t* out, const g1j& p) {
+  dc_st8(out, p.x);
+  dc_st8(out + 8, p.y);
+  dc_st8(out + 16, p.z);
+}
+template <int OP>
+FTS_HD void dc_g1_apply(const uint32_t* in, uint32_t* out) {
+  if constexpr (OP == DC_g1f_dbl) {
+    const j29 p = {dc_ld29(in), dc_ld29(in + 9), dc_ld29(in + 18), in[27] != 0};
+    dc_stj(out, j29_to(j29_dbl(p)));
+    dc_stj(out + 24, jac_dbl(j29_to(p)));
+  } else if constexpr (OP == DC_g1f_madd) {
+    const j29 p = {dc_ld29(in), dc_ld29(in + 9), dc_ld29(in + 18), in[27] != 0};
+    const f29 x2 = dc_ld29(in + 28), y2 = dc_ld29(in + 37);
+    dc_stj(out, j29_to(j29_madd(p, x2, y2)));
+    dc_stj(out + 24, jac_add_aff(j29_to(p), g1a{f29_to_fp(x2), f29_to_fp(y2), false}));
+  } else {
+    static_assert(OP == DC_g1f_xmadd, "dc_g1_apply: op without a branch");
+    const x29 p = {dc_ld29(in), dc_ld29(in + 9), dc_ld29(in + 18), dc_ld29(in + 27), in[36] != 0};
+    const f29 x2 = dc_ld29(in + 37), y2 = dc_ld29(in + 46);
+    dc_stj(out, j29_to(x29_to_j29(x29_madd(p, x2, y2))));
+    dc_stj(out + 24, jac_add_aff(j29_to(x29_to_j29(p)), g1a{f29_to_fp(x2), f29_to_fp(y2), false}));
+  }
+}
+
 // SHA-256 of one message given as nseg (offset, length) segments of an arena:
 // out[0..7] the digest bytes as they lie in memory, out[8..15] digest_mod_r
 FTS_HD void dc_sha(const uint8_t* arena, const uint32_t* segs, uint32_t nseg, uint32_t* out) {
