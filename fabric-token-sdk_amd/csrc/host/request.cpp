@@ -95,6 +95,37 @@ std::string der_token_request(const uint8_t* raw, size_t len, std::vector<Slice>
   return "";
 }
 
+void signed_message(const uint8_t* raw, size_t len, const uint8_t* binding, size_t binding_len,
+                    std::vector<uint8_t>& out) {
+  out.clear();
+  Der d{raw, len};
+  size_t off = 0, body, l0, l1;
+  if (der_header(d, off, 0x30, body)) return;  // not a request der_token_request accepts
+  const size_t a = off;                        // the Issues field starts here
+  if (der_header(d, off, 0x30, l0)) return;
+  off += l0;
+  if (der_header(d, off, 0x30, l1)) return;
+  off += l1;
+  const size_t inner = off - a + 4;  // Issues, Transfers, and 30 00 30 00 for the two nil slices
+  uint8_t hdr[2 + sizeof(size_t)];
+  size_t hn = 0;
+  hdr[hn++] = 0x30;
+  if (inner < 0x80) {
+    hdr[hn++] = (uint8_t)inner;
+  } else {
+    int nb = 0;
+    for (size_t v = inner; v; v >>= 8) nb++;
+    hdr[hn++] = (uint8_t)(0x80 | nb);
+    for (int k = nb - 1; k >= 0; k--) hdr[hn++] = (uint8_t)(inner >> (8 * k));
+  }
+  static const uint8_t NIL2[4] = {0x30, 0x00, 0x30, 0x00};
+  out.reserve(hn + inner + binding_len);
+  out.insert(out.end(), hdr, hdr + hn);
+  out.insert(out.end(), raw + a, raw + off);
+  out.insert(out.end(), NIL2, NIL2 + 4);
+  if (binding_len) out.insert(out.end(), binding, binding + binding_len);
+}
+
 // ---------------------------------------------------------------- JSON actions
 namespace {
 
@@ -228,7 +259,10 @@ std::string dec_transfer_action(const uint8_t* p, size_t n, TransferAct& a, std:
   return check_metadata(d, d.field(root, "Metadata"));
 }
 
-std::string dec_issue_action(const uint8_t* p, size_t n, IssueAct& a, std::vector<uint8_t>& pool) {
+namespace {
+// issuer: where the Issuer bytes go (nullptr: checked, not kept)
+std::string dec_issue(const uint8_t* p, size_t n, IssueAct& a, std::vector<uint8_t>& pool,
+                      std::vector<uint8_t>* issuer) {
   a = IssueAct();
   std::string err;
   bool is_null;
@@ -237,7 +271,11 @@ std::string dec_issue_action(const uint8_t* p, size_t n, IssueAct& a, std::vecto
   if (is_null) return "";
   uint32_t root = d.root();
   static thread_local std::vector<uint8_t> tmp;
-  if (dec_bytes(d, d.field(root, "Issuer"), tmp) == D_ERR) return "bad Issuer";
+  if (issuer) {
+    if (dec_bytes_append(d, d.field(root, "Issuer"), *issuer) == D_ERR) return "bad Issuer";
+  } else if (dec_bytes(d, d.field(root, "Issuer"), tmp) == D_ERR) {
+    return "bad Issuer";
+  }
   // OutputTokens carries the tag json:"outputs,omitempty" (issue.go:24)
   err = dec_outputs(d, d.field(root, "outputs"), a.out, pool);
   if (!err.empty()) return err;
@@ -246,7 +284,9 @@ std::string dec_issue_action(const uint8_t* p, size_t n, IssueAct& a, std::vecto
   return check_metadata(d, d.field(root, "Metadata"));
 }
 
-std::string dec_token(const uint8_t* p, size_t n, ElemRef& data, std::vector<uint8_t>& pool) {
+// owners: where the Owner bytes are appended (nullptr: checked, not kept)
+std::string dec_tok(const uint8_t* p, size_t n, ElemRef& data, std::vector<uint8_t>& pool,
+                    std::vector<uint8_t>* owners) {
   data = ElemRef{D_NIL, 0, 0};
   std::string err;
   bool is_null;
@@ -255,10 +295,38 @@ std::string dec_token(const uint8_t* p, size_t n, ElemRef& data, std::vector<uin
   if (is_null) return "";
   uint32_t root = d.root();
   static thread_local std::vector<uint8_t> tmp;
-  if (dec_bytes(d, d.field(root, "Owner"), tmp) == D_ERR) return "bad Owner";
+  if (owners) {
+    if (dec_bytes_append(d, d.field(root, "Owner"), *owners) == D_ERR) return "bad Owner";
+  } else if (dec_bytes(d, d.field(root, "Owner"), tmp) == D_ERR) {
+    return "bad Owner";
+  }
   if (dec_g1(d, d.field(root, "Data"), data, pool) == D_ERR) return "bad Data";
   if (data.st == D_OK && data.bad) return "bad Data";
   return "";
+}
+}  // namespace
+
+std::string dec_issue_action(const uint8_t* p, size_t n, IssueAct& a, std::vector<uint8_t>& pool) {
+  return dec_issue(p, n, a, pool, nullptr);
+}
+
+std::string dec_issue_action_issuer(const uint8_t* p, size_t n, IssueAct& a, std::vector<uint8_t>& pool,
+                                    std::vector<uint8_t>& issuer) {
+  issuer.clear();
+  return dec_issue(p, n, a, pool, &issuer);
+}
+
+std::string dec_token(const uint8_t* p, size_t n, ElemRef& data, std::vector<uint8_t>& pool) {
+  return dec_tok(p, n, data, pool, nullptr);
+}
+
+std::string dec_token_owner(const uint8_t* p, size_t n, ElemRef& data, std::vector<uint8_t>& pool,
+                            std::vector<uint8_t>& owners, size_t& owner_len) {
+  const size_t at = owners.size();
+  std::string e = dec_tok(p, n, data, pool, &owners);
+  if (!e.empty()) owners.resize(at);
+  owner_len = owners.size() - at;
+  return e;
 }
 
 }  // namespace ftsh
@@ -301,6 +369,27 @@ struct IRef {
   size_t r, k, out_off;
 };
 
+// What the signed path keeps per request beside ReqState (Chunk.sg, sized in
+// signed calls only).  A check's verdict is 0 or the code of the table in
+// include/ftsamd.h; the walk of finish_chunk reads them in the reference's order.
+struct SigState {
+  bool asn1_failed = false;                  // row 1 (ReqState.failed then also covers row 3)
+  std::vector<uint8_t> msg;                  // the signed message; every item of the request points at it
+  std::vector<Slice> sigs;                   // AuditorSignatures ++ Signatures, or Signatures alone
+  int32_t aud = 0;                           // row 2
+  std::vector<std::vector<uint8_t>> issuer;  // per issue action: Issuer
+  std::vector<int32_t> is_sig;               // per issue action: rows 5-6
+  std::vector<uint8_t> owners;               // Owner bytes of the loaded inputs, back to back
+  std::vector<std::vector<Slice>> own;       // per transfer, per loaded input: its Owner (p = offset into owners)
+  std::vector<size_t> nin;                   // per transfer: the leading inputs that passed row 7
+  std::vector<std::vector<int32_t>> in_sig;  // per transfer, per such input: rows 8-9
+};
+// where a signature item's verdict goes: t < 0 the auditor's, j < 0 issue action t's, else input j of transfer t
+struct SRef {
+  size_t r;
+  int32_t t, j;
+};
+
 // One pipeline step: requests [r0, r1) from decode to the engine's verdicts.
 struct Chunk {
   size_t r0 = 0, r1 = 0;
@@ -313,9 +402,19 @@ struct Chunk {
   std::vector<int32_t> tcodes, icodes;
   int trc = FTZ_SUCCESS, irc = FTZ_SUCCESS;
   std::thread th_t, th_i;
+  // the signature stage (signed calls): the chunk's owner and x509 items, their verdicts, their threads
+  std::vector<SigState> sg;
+  std::vector<ftz_owner_sig> ov;
+  std::vector<ftz_ecdsa_sig> ev;
+  std::vector<SRef> orefs, erefs;
+  std::vector<int32_t> ocodes, ecodes;
+  int orc = FTZ_SUCCESS, erc = FTZ_SUCCESS;
+  std::thread th_o, th_e;
   void join() {
     if (th_t.joinable()) th_t.join();
     if (th_i.joinable()) th_i.join();
+    if (th_o.joinable()) th_o.join();
+    if (th_e.joinable()) th_e.join();
   }
 };
 
@@ -359,10 +458,12 @@ void par_each(const RequestHooks& h, size_t m, const std::function<void(size_t)>
   });
 }
 
-int decode_chunk(const ftz_bytes* reqs, const RequestHooks& h, Chunk& c, RequestStats* stats, std::string& err) {
+int decode_chunk(const ftz_bytes* reqs, const RequestHooks& h, Chunk& c, RequestStats* stats, std::string& err,
+                 const RequestSigners* sg = nullptr) {
   const size_t m = c.r1 - c.r0;
   StageClock clk{stats};
   c.st.resize(m);
+  if (sg) c.sg.resize(m);
   auto each = [&](const std::function<void(size_t)>& f) { par_each(h, m, f); };
   std::vector<size_t> cnt(m + 1, 0);
   // 1. decode: ASN.1, then every issue action, then every transfer action
@@ -373,9 +474,26 @@ int decode_chunk(const ftz_bytes* reqs, const RequestHooks& h, Chunk& c, Request
     const ftz_bytes& q = reqs[c.r0 + i];
     static thread_local std::vector<Slice> f[4];  // cleared by der_token_request
     std::string e = der_token_request(q.p, q.len, f);
-    if (e.empty()) {
+    if (sg) {
+      // the signed message and the signature list come before anything else of
+      // the request is looked at (validator.go:57-75)
+      SigState& g = c.sg[i];
+      g.asn1_failed = !e.empty();
+      if (e.empty()) {
+        const ftz_bytes& bd = sg->bindings[c.r0 + i];
+        signed_message(q.p, q.len, bd.p, bd.len, g.msg);
+        if (sg->auditor.len != 0) g.sigs.assign(f[3].begin(), f[3].end());
+        g.sigs.insert(g.sigs.end(), f[2].begin(), f[2].end());
+        s.is.resize(f[0].size());
+        g.issuer.resize(f[0].size());
+        for (size_t k = 0; k < f[0].size() && e.empty(); k++)
+          e = dec_issue_action_issuer(f[0][k].p, f[0][k].len, s.is[k], s.pool, g.issuer[k]);
+      }
+    } else if (e.empty()) {
       s.is.resize(f[0].size());
       for (size_t k = 0; k < f[0].size() && e.empty(); k++) e = dec_issue_action(f[0][k].p, f[0][k].len, s.is[k], s.pool);
+    }
+    if (e.empty()) {
       s.tr.resize(f[1].size());
       for (size_t k = 0; k < f[1].size() && e.empty(); k++) e = dec_transfer_action(f[1][k].p, f[1][k].len, s.tr[k], s.pool);
     }
@@ -418,7 +536,90 @@ int decode_chunk(const ftz_bytes* reqs, const RequestHooks& h, Chunk& c, Request
   return FTZ_SUCCESS;
 }
 
-int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err) {
+// The signature stage of a chunk: one x509 item per auditor and issuer check,
+// one owner item per input that passed row 7, all of a request over the same
+// message pointer (the pipelines lay a message out once per distinct pointer).
+// The index of a check's signature follows from the counts alone: every check
+// before it consumed one, or the walk has ended.  A check that finds the list
+// exhausted still goes to its pipeline with an empty signature: the verifier is
+// built first (identity and owner errors), and no empty signature unmarshals.
+void sign_chunk(const RequestSigners& sg, Chunk& c) {
+  const size_t m = c.r1 - c.r0;
+  auto sig_at = [](const SigState& g, size_t k) { return k < g.sigs.size() ? g.sigs[k] : Slice{nullptr, 0}; };
+  for (size_t r = 0; r < m; r++) {
+    const ReqState& s = c.st[r];
+    SigState& g = c.sg[r];
+    if (g.asn1_failed) continue;
+    size_t cur = 0;
+    if (sg.has_auditor) {
+      if (sg.auditor.len == 0) {
+        g.aud = FTZ_ERR_IDENTITY;  // an empty identity gives no verifier
+      } else if (!sg.verify_ecdsa) {
+        g.aud = FTZ_ERR_UNSUPPORTED;
+      } else if (sg.auditor_key.code) {
+        g.aud = sg.auditor_key.code;
+      } else {
+        const Slice sig = sig_at(g, cur);
+        c.erefs.push_back(SRef{r, -1, -1});
+        c.ev.push_back(ftz_ecdsa_sig{nullptr, 0, sg.auditor_key.key, g.msg.data(), g.msg.size(), sig.p, sig.len});
+      }
+      cur++;
+    }
+    if (s.failed || g.aud) continue;  // rows 2 and 3 end the walk
+    g.is_sig.assign(s.is.size(), 0);
+    for (size_t k = 0; k < s.is.size(); k++, cur++) {
+      const std::vector<uint8_t>& id = g.issuer[k];
+      int32_t key = -1;
+      if (!sg.issuers.empty()) {
+        size_t at = 0;
+        while (at < sg.issuers.size() &&
+               !(sg.issuers[at].len == id.size() && (id.empty() || memcmp(sg.issuers[at].p, id.data(), id.size()) == 0)))
+          at++;
+        if (at == sg.issuers.size()) {
+          g.is_sig[k] = FTZ_ERR_ISSUER;
+          continue;
+        }
+        if (!sg.verify_ecdsa || at >= sg.issuer_keys.size()) {
+          g.is_sig[k] = FTZ_ERR_UNSUPPORTED;
+          continue;
+        }
+        if (sg.issuer_keys[at].code) {
+          g.is_sig[k] = sg.issuer_keys[at].code;
+          continue;
+        }
+        key = sg.issuer_keys[at].key;
+      } else if (!sg.verify_ecdsa) {
+        g.is_sig[k] = FTZ_ERR_UNSUPPORTED;
+        continue;
+      }
+      const Slice sig = sig_at(g, cur);
+      c.erefs.push_back(SRef{r, (int32_t)k, -1});
+      c.ev.push_back(ftz_ecdsa_sig{key < 0 ? id.data() : nullptr, key < 0 ? id.size() : 0, key, g.msg.data(),
+                                   g.msg.size(), sig.p, sig.len});
+    }
+    g.in_sig.resize(s.tr.size());
+    for (size_t t = 0; t < s.tr.size(); cur += s.tr[t].inputs.size(), t++) {
+      g.in_sig[t].assign(g.nin[t], sg.verify_owners ? 0 : FTZ_ERR_UNSUPPORTED);
+      if (!sg.verify_owners) continue;
+      for (size_t j = 0; j < g.nin[t]; j++) {
+        const Slice o = g.own[t][j], sig = sig_at(g, cur + j);
+        c.orefs.push_back(SRef{r, (int32_t)t, (int32_t)j});
+        c.ov.push_back(ftz_owner_sig{g.owners.data() + reinterpret_cast<uintptr_t>(o.p), o.len, g.msg.data(),
+                                     g.msg.size(), sig.p, sig.len});
+      }
+    }
+  }
+  c.ocodes.resize(c.ov.size());
+  c.ecodes.resize(c.ev.size());
+  Chunk* cp = &c;
+  const RequestSigners* sp = &sg;
+  if (!c.ov.empty())
+    c.th_o = std::thread([sp, cp] { cp->orc = sp->verify_owners(cp->ov.size(), cp->ov.data(), cp->ocodes.data()); });
+  if (!c.ev.empty())
+    c.th_e = std::thread([sp, cp] { cp->erc = sp->verify_ecdsa(cp->ev.size(), cp->ev.data(), cp->ecodes.data()); });
+}
+
+int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err, const RequestSigners* sg = nullptr) {
   const size_t m = c.r1 - c.r0;
   StageClock clk{h.stats};
   auto each = [&](const std::function<void(size_t)>& f) { par_each(h, m, f); };
@@ -432,6 +633,11 @@ int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err) {
     s.ins.resize(s.tr.size());
     s.tr_pre.assign(s.tr.size(), 0);
     s.is_pre.assign(s.is.size(), 0);
+    if (sg) {
+      SigState& g = c.sg[r];
+      g.own.resize(s.tr.size());
+      g.nin.assign(s.tr.size(), 0);
+    }
     size_t k = 0;
     for (const TransferAct& t : s.tr) k += t.inputs.size();
     kat[r + 1] = k;
@@ -491,14 +697,21 @@ int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err) {
           break;
         }
         ElemRef d;
-        if (!dec_token(vals[k].p, vals[k].len, d, s.pool).empty()) {
+        size_t at = 0, ol = 0;
+        if (sg) at = c.sg[r].owners.size();
+        if (!(sg ? dec_token_owner(vals[k].p, vals[k].len, d, s.pool, c.sg[r].owners, ol)
+                 : dec_token(vals[k].p, vals[k].len, d, s.pool))
+                 .empty()) {
           s.tr_pre[t] = FTZ_ERR_INPUT;  // "failed to deserialize input to spend"
           break;
         }
         s.ins[t].push_back(d);
+        if (sg) c.sg[r].own[t].push_back(Slice{reinterpret_cast<const uint8_t*>(at), ol});
       }
       k = k1;
-      if (!s.tr_pre[t])
+      if (sg) c.sg[r].nin[t] = s.ins[t].size();
+      // signed: an input loaded before a missing one is still checked, its row 7 comes first
+      if (!s.tr_pre[t] || sg)
         for (const ElemRef& d : s.ins[t]) nd += d.st == D_OK;
     }
     cnt[r + 1] = nd;
@@ -507,18 +720,21 @@ int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err) {
   prefix(cnt);
   if (cnt[m]) {
     std::vector<uint8_t> slots(64 * cnt[m]), ok(cnt[m]);
-    std::vector<uint32_t> tr_of(cnt[m]);
+    std::vector<uint32_t> tr_of(cnt[m]), in_of(sg ? cnt[m] : 0);
     each([&](size_t r) {
       const ReqState& s = c.st[r];
       size_t o = cnt[r];
       if (s.failed) return;
       for (size_t t = 0; t < s.tr.size(); t++) {
-        if (s.tr_pre[t]) continue;
-        for (const ElemRef& d : s.ins[t])
+        if (s.tr_pre[t] && !sg) continue;
+        for (size_t j = 0; j < s.ins[t].size(); j++) {
+          const ElemRef& d = s.ins[t][j];
           if (d.st == D_OK) {
             memcpy(slots.data() + 64 * o, s.pool.data() + d.off, 64);
+            if (sg) in_of[o] = (uint32_t)j;
             tr_of[o++] = (uint32_t)t;
           }
+        }
       }
     });
     int rc = h.check(cnt[m], slots.data(), ok.data());
@@ -528,7 +744,10 @@ int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err) {
     }
     each([&](size_t r) {
       for (size_t k = cnt[r]; k < cnt[r + 1]; k++)
-        if (!ok[k]) c.st[r].tr_pre[tr_of[k]] = FTZ_ERR_INPUT;
+        if (!ok[k]) {
+          c.st[r].tr_pre[tr_of[k]] = FTZ_ERR_INPUT;
+          if (sg) c.sg[r].nin[tr_of[k]] = std::min<size_t>(c.sg[r].nin[tr_of[k]], in_of[k]);
+        }
     });
   }
   clk.mark(&RequestStats::check);
@@ -618,6 +837,7 @@ int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err) {
   // issues and transfers on helper threads: the job engine coalesces them (and
   // the other chunks in flight) into shared device batches
   Chunk* cp = &c;
+  if (sg) sign_chunk(*sg, c);
   if (!c.iv.empty())
     c.th_i = std::thread([&h, cp] { cp->irc = h.verify_issues(cp->iv.size(), cp->iv.data(), cp->icodes.data()); });
   if (!c.tv.empty())
@@ -626,6 +846,25 @@ int ledger_chunk(const RequestHooks& h, Chunk& c, std::string& err) {
 }
 
 // 5. the chunk's verdicts: first failure in the reference's order, issues then transfers
+// the signed walk of one request (the table of include/ftsamd.h, rows 1-10)
+void signed_verdict(const ReqState& s, const SigState& g, int32_t& code, int32_t& at) {
+  code = FTZ_OK, at = -1;
+  if (g.asn1_failed) code = FTZ_ERR_PARSE;
+  if (code == FTZ_OK) code = g.aud;
+  if (code == FTZ_OK && s.failed) code = s.code;
+  if (code != FTZ_OK) return;
+  for (size_t k = 0; k < s.is.size(); k++) {
+    code = s.is_pre[k] ? s.is_pre[k] : g.is_sig[k];
+    if (code != FTZ_OK) return (void)(at = (int32_t)k);
+  }
+  for (size_t t = 0; t < s.tr.size(); t++) {
+    for (size_t j = 0; j < g.nin[t] && code == FTZ_OK; j++) code = g.in_sig[t][j];
+    if (code == FTZ_OK && g.nin[t] < s.tr[t].inputs.size()) code = FTZ_ERR_INPUT;
+    if (code == FTZ_OK) code = s.tr_pre[t];
+    if (code != FTZ_OK) return (void)(at = (int32_t)(s.is.size() + t));
+  }
+}
+
 int finish_chunk(Chunk& c, int32_t* codes, int32_t* failed, std::string& err) {
   c.join();
   if (c.irc != FTZ_SUCCESS || c.trc != FTZ_SUCCESS) {
@@ -634,6 +873,24 @@ int finish_chunk(Chunk& c, int32_t* codes, int32_t* failed, std::string& err) {
   }
   for (size_t k = 0; k < c.irefs.size(); k++) c.st[c.irefs[k].r].is_pre[c.irefs[k].k] = c.icodes[k];
   for (size_t k = 0; k < c.trefs.size(); k++) c.st[c.trefs[k].r].tr_pre[c.trefs[k].t] = c.tcodes[k];
+  if (!c.sg.empty()) {
+    if (c.orc != FTZ_SUCCESS || c.erc != FTZ_SUCCESS) {
+      err = c.orc != FTZ_SUCCESS ? "owner signature verification failed" : "x509 signature verification failed";
+      return c.orc != FTZ_SUCCESS ? c.orc : c.erc;
+    }
+    for (size_t k = 0; k < c.orefs.size(); k++) c.sg[c.orefs[k].r].in_sig[c.orefs[k].t][c.orefs[k].j] = c.ocodes[k];
+    for (size_t k = 0; k < c.erefs.size(); k++) {
+      const SRef& e = c.erefs[k];
+      (e.t < 0 ? c.sg[e.r].aud : c.sg[e.r].is_sig[e.t]) = c.ecodes[k];
+    }
+    for (size_t i = 0; i < c.st.size(); i++) {
+      int32_t code, at;
+      signed_verdict(c.st[i], c.sg[i], code, at);
+      codes[c.r0 + i] = code;
+      if (failed) failed[c.r0 + i] = at;
+    }
+    return FTZ_SUCCESS;
+  }
   for (size_t i = 0; i < c.st.size(); i++) {
     const ReqState& s = c.st[i];
     int32_t code = s.failed ? s.code : FTZ_OK, at = -1;
@@ -651,8 +908,9 @@ int finish_chunk(Chunk& c, int32_t* codes, int32_t* failed, std::string& err) {
 
 }  // namespace
 
-int verify_token_requests(size_t n, const ftz_bytes* reqs, const RequestHooks& h, int32_t* codes, int32_t* failed,
-                          std::string& err) {
+namespace {
+int run_pipeline(size_t n, const ftz_bytes* reqs, const RequestHooks& h, const RequestSigners* sg, int32_t* codes,
+                 int32_t* failed, std::string& err) {
   const size_t CH = h.chunk ? h.chunk : 8192, IN = h.inflight ? h.inflight : 1;
   std::deque<std::unique_ptr<Chunk>> fly;
   int rc = FTZ_SUCCESS;
@@ -680,8 +938,8 @@ int verify_token_requests(size_t n, const ftz_bytes* reqs, const RequestHooks& h
     clk.mark(&RequestStats::drain);
     if (rc != FTZ_SUCCESS) break;
     fly.push_back(make());
-    rc = decode_chunk(reqs, h, *fly.back(), h.stats, err);
-    if (rc == FTZ_SUCCESS) rc = ledger_chunk(h, *fly.back(), err);
+    rc = decode_chunk(reqs, h, *fly.back(), h.stats, err, sg);
+    if (rc == FTZ_SUCCESS) rc = ledger_chunk(h, *fly.back(), err, sg);
   }
   // drain (also after an error: every helper thread is joined before returning)
   StageClock clk{h.stats};
@@ -696,6 +954,21 @@ int verify_token_requests(size_t n, const ftz_bytes* reqs, const RequestHooks& h
   }
   clk.mark(&RequestStats::drain);
   return rc;
+}
+}  // namespace
+
+int verify_token_requests(size_t n, const ftz_bytes* reqs, const RequestHooks& h, int32_t* codes, int32_t* failed,
+                          std::string& err) {
+  return run_pipeline(n, reqs, h, nullptr, codes, failed, err);
+}
+
+int verify_signed_token_requests(size_t n, const ftz_bytes* reqs, const RequestHooks& h, const RequestSigners& sg,
+                                 int32_t* codes, int32_t* failed, std::string& err) {
+  if (n && !sg.bindings) {
+    err = "null bindings";
+    return FTZ_E_INVALID;
+  }
+  return run_pipeline(n, reqs, h, &sg, codes, failed, err);
 }
 
 }  // namespace ftsh

@@ -61,6 +61,22 @@ std::string dec_transfer_action(const uint8_t* p, size_t n, TransferAct& a, std:
 std::string dec_issue_action(const uint8_t* p, size_t n, IssueAct& a, std::vector<uint8_t>& pool);
 // token.Token of a ledger input: "" and the Data element, or an error
 std::string dec_token(const uint8_t* p, size_t n, ElemRef& data, std::vector<uint8_t>& pool);
+// the same decoders for the signed request path, which needs the signer of
+// each action: the issue action's Issuer, and the ledger token's Owner appended
+// to `owners` (`owner_len` bytes; JSON null = no bytes)
+std::string dec_issue_action_issuer(const uint8_t* p, size_t n, IssueAct& a, std::vector<uint8_t>& pool,
+                                    std::vector<uint8_t>& issuer);
+std::string dec_token_owner(const uint8_t* p, size_t n, ElemRef& data, std::vector<uint8_t>& pool,
+                            std::vector<uint8_t>& owners, size_t& owner_len);
+
+// The message every signature of a request covers (validator.go:57-66):
+// asn1.Marshal(TokenRequest{Issues, Transfers}) || binding.  `raw` must have
+// passed der_token_request: it is minimal DER, so the first two fields are
+// copied as they stand under a recomputed outer header, followed by the two
+// empty SEQUENCEs of the nil Signatures / AuditorSignatures.  Nothing after
+// the second field of `raw` enters the message.
+void signed_message(const uint8_t* raw, size_t len, const uint8_t* binding, size_t binding_len,
+                    std::vector<uint8_t>& out);
 
 }  // namespace ftsh
 
@@ -101,6 +117,31 @@ struct RequestHooks {
   size_t inflight = FTS_REQ_INFLIGHT;  // chunks whose ZK verification may be in flight at once
   RequestStats* stats = nullptr;
 };
+
+// ---- the signed request path: the same pipeline plus the auditor's, the
+// issuers' and the owners' signatures (VerifyTokenRequestFromRaw in full, minus
+// HTLC scripts and metadata counting).  The x509 side is reached only through
+// the hook, so this file needs nothing of the ECDSA host code.
+struct SignerKey {
+  int32_t key = -1;  // index the ecdsa hook knows the identity by (code == 0)
+  int32_t code = 0;  // != 0: the identity does not give a verifier (FTZ_ERR_IDENTITY / _UNSUPPORTED)
+};
+struct RequestSigners {
+  // thread-safe, shaped like ftz_verify_owner_signatures / ftz_verify_ecdsa_signatures;
+  // unset: every check that needs the hook is FTZ_ERR_UNSUPPORTED
+  std::function<int(size_t n, const ftz_owner_sig* s, int32_t* codes)> verify_owners;
+  std::function<int(size_t n, const ftz_ecdsa_sig* s, int32_t* codes)> verify_ecdsa;
+  bool has_auditor = false;  // PublicParams.Auditor != nil
+  Slice auditor{nullptr, 0};
+  SignerKey auditor_key;           // read when auditor.len != 0
+  std::vector<Slice> issuers;      // PublicParams.Issuers (empty: any issuer, decoded per item)
+  std::vector<SignerKey> issuer_keys;
+  const ftz_bytes* bindings = nullptr;  // per request: the txID string
+};
+// As verify_token_requests, with the signature checks in the reference's order
+// (include/ftsamd.h ftz_verify_signed_token_requests).  h.get_states only.
+int verify_signed_token_requests(size_t n, const ftz_bytes* reqs, const RequestHooks& h, const RequestSigners& sg,
+                                 int32_t* codes, int32_t* failed, std::string& err);
 
 // codes[r]: FTZ_OK or the first failing check of request r in the reference's
 // order; failed[r] (optional): the failing action's index (issues first, then

@@ -31,8 +31,10 @@ extern "C" int ftz_token_request_decode(const uint8_t* raw, size_t len, size_t c
 }
 
 namespace {
+// sg: the signature stage of ftz_verify_signed_token_requests (nullptr: the proofs alone)
 int verify_requests(ftz_ctx* ctx, size_t n, const ftz_bytes* reqs, ftz_get_state_fn get_state,
-                    ftz_get_states_fn get_states, void* user, int32_t* codes, int32_t* failed_action) {
+                    ftz_get_states_fn get_states, void* user, int32_t* codes, int32_t* failed_action,
+                    const ftsh::RequestSigners* sg = nullptr) {
   if (!ctx || (n && (!reqs || !codes))) return set_err(FTZ_E_INVALID, "null argument");
   for (size_t i = 0; i < n; i++)
     if (!reqs[i].p && reqs[i].len) return set_err(FTZ_E_INVALID, "null request with non-zero length");
@@ -85,7 +87,8 @@ int verify_requests(ftz_ctx* ctx, size_t n, const ftz_bytes* reqs, ftz_get_state
   ftsh::RequestStats st;
   h.stats = &st;
   std::string err;
-  int rc = ftsh::verify_token_requests(n, reqs, h, codes, failed_action, err);
+  int rc = sg ? ftsh::verify_signed_token_requests(n, reqs, h, *sg, codes, failed_action, err)
+              : ftsh::verify_token_requests(n, reqs, h, codes, failed_action, err);
   {
     std::lock_guard<std::mutex> lk(ctx->req_mu);
     const double v[6] = {st.decode, st.check, st.lookup, st.tokens, st.build, st.drain};
@@ -119,4 +122,54 @@ extern "C" int ftz_verify_token_requests_batched(ftz_ctx* ctx, size_t n, const f
                                                  int32_t* failed_action) {
   if (!get_states) return set_err(FTZ_E_INVALID, "null get_states");
   return verify_requests(ctx, n, reqs, nullptr, get_states, user, codes, failed_action);
+}
+
+// x509 identity -> how the signature stage names it: registered on the handle
+// (idempotent per identity bytes), or the code its requests get
+static int signer_key(ftz_ecdsa* ec, const uint8_t* id, size_t len, ftsh::SignerKey& out) {
+  out = ftsh::SignerKey();
+  if (ftz_ecdsa_add_identity(ec, id, len, &out.key) == FTZ_SUCCESS) return FTZ_SUCCESS;
+  std::string why = ftz_last_error();
+  uint8_t xy[64];
+  int code = ftz_x509_public_key(id, len, xy);
+  if (code == FTZ_ERR_IDENTITY || code == FTZ_ERR_UNSUPPORTED) {
+    out.code = code;
+    return FTZ_SUCCESS;
+  }
+  return set_err(FTZ_E_INVALID, why);  // a decodable P-256 identity that found no room on the handle
+}
+
+extern "C" int ftz_verify_signed_token_requests(ftz_ctx* ctx, const ftz_request_signers* signers, size_t n,
+                                                const ftz_signed_request* reqs, ftz_get_states_fn get_states,
+                                                void* user, int32_t* codes, int32_t* failed_action) {
+  if (!ctx || !signers || (n && (!reqs || !codes))) return set_err(FTZ_E_INVALID, "null argument");
+  if (!get_states) return set_err(FTZ_E_INVALID, "null get_states");
+  if (signers->n_issuers && !signers->issuers) return set_err(FTZ_E_INVALID, "null issuers");
+  for (size_t i = 0; i < signers->n_issuers; i++)
+    if (!signers->issuers[i].p && signers->issuers[i].len) return set_err(FTZ_E_INVALID, "null issuer with non-zero length");
+  for (size_t i = 0; i < n; i++)
+    if (!reqs[i].binding.p && reqs[i].binding.len) return set_err(FTZ_E_INVALID, "null binding with non-zero length");
+  ftsh::RequestSigners sg;
+  ftz_idemix* ix = signers->ix;
+  ftz_ecdsa* ec = signers->ec;
+  if (ix) sg.verify_owners = [ix](size_t m, const ftz_owner_sig* s, int32_t* c) { return ftz_verify_owner_signatures(ix, m, s, c); };
+  if (ec) sg.verify_ecdsa = [ec](size_t m, const ftz_ecdsa_sig* s, int32_t* c) { return ftz_verify_ecdsa_signatures(ec, m, s, c); };
+  sg.has_auditor = signers->auditor != nullptr;
+  sg.auditor = ftsh::Slice{signers->auditor, signers->auditor ? signers->auditor_len : 0};
+  if (ec && sg.auditor.len) {
+    int rc = signer_key(ec, sg.auditor.p, sg.auditor.len, sg.auditor_key);
+    if (rc != FTZ_SUCCESS) return rc;
+  }
+  sg.issuers.resize(signers->n_issuers);
+  sg.issuer_keys.resize(signers->n_issuers);
+  for (size_t i = 0; i < signers->n_issuers; i++) {
+    sg.issuers[i] = ftsh::Slice{signers->issuers[i].p, signers->issuers[i].len};
+    if (!ec) continue;
+    int rc = signer_key(ec, sg.issuers[i].p, sg.issuers[i].len, sg.issuer_keys[i]);
+    if (rc != FTZ_SUCCESS) return rc;
+  }
+  std::vector<ftz_bytes> raw(n), bind(n);
+  for (size_t i = 0; i < n; i++) raw[i] = reqs[i].raw, bind[i] = reqs[i].binding;
+  sg.bindings = bind.data();
+  return verify_requests(ctx, n, raw.data(), nullptr, get_states, user, codes, failed_action, &sg);
 }

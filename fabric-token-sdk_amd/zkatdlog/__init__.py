@@ -292,6 +292,46 @@ class Context:
         self.verify_token_requests_packed(arr, n, ledger, codes, failed, batched=batched)
         return list(codes)[:n], list(failed)[:n]
 
+    def verify_signed_token_requests(self, requests, bindings, ledger, idemix=None, ecdsa=None, auditor=None,
+                                     issuers=()):
+        """Validator.VerifyTokenRequestFromRaw with its signature checks
+        (ftz_verify_signed_token_requests): requests and their bindings (the
+        txID strings), the ledger as for verify_token_requests (always the
+        batched lookup), the Idemix handle for the owners' signatures and the
+        Ecdsa handle for the auditor's and the issuers' (None: those checks
+        answer FTZ_ERR_UNSUPPORTED), PublicParams.Auditor (None = nil, b"" =
+        the empty non-nil slice) and PublicParams.Issuers.  Returns (codes,
+        failed_action) lists."""
+        arr, keep = _abi.pack_signed_requests(requests, bindings)
+        n = len(keep[0])
+        codes = (ctypes.c_int32 * max(1, n))()
+        failed = (ctypes.c_int32 * max(1, n))()
+        self.verify_signed_token_requests_packed(arr, n, ledger, codes, failed, idemix, ecdsa, auditor, issuers)
+        return list(codes)[:n], list(failed)[:n]
+
+    def verify_signed_token_requests_packed(self, arr, n, ledger, codes, failed, idemix=None, ecdsa=None,
+                                            auditor=None, issuers=()):
+        """as verify_signed_token_requests over a packed ftz_signed_request array
+        (_abi.pack_signed_requests) and caller-owned int32 code arrays"""
+        sg = _abi.RequestSigners()
+        sg.ix = idemix._h if idemix is not None else None
+        sg.ec = ecdsa._h if ecdsa is not None else None
+        aud = None
+        if auditor is not None:
+            aud = ctypes.create_string_buffer(bytes(auditor), max(1, len(auditor)))
+            sg.auditor, sg.auditor_len = ctypes.addressof(aud), len(auditor)
+        ia, ikeep = _abi.pack_bytes(issuers)
+        sg.issuers, sg.n_issuers = ia, len(ikeep)
+        if isinstance(ledger, NativeLedger):
+            fn, user = ledger.fn(True), ledger.handle
+            keep_cb = None
+        else:
+            keep_cb = _abi.get_states_callback(ledger)
+            fn, user = ctypes.cast(keep_cb, ctypes.c_void_p), None
+        _check(self._lib.ftz_verify_signed_token_requests(self._h, ctypes.byref(sg), n, arr, fn, user, codes, failed),
+               self._lib)
+        del keep_cb, aud, ikeep
+
     def request_stats(self, reset=False):
         """calling-thread ms per request-pipeline stage (ftz_ctx_request_stats)"""
         ms = (ctypes.c_double * 6)()

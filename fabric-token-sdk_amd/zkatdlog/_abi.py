@@ -224,7 +224,33 @@ GET_STATE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, 
 GET_STATES_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p)
 FTZ_ERR_INPUT = 8
 FTZ_ERR_PS_SIGNATURE = 14
+FTZ_ERR_ISSUER = 15
 MESSAGES[FTZ_ERR_PS_SIGNATURE] = "invalid Pointcheval-Sanders signature"
+MESSAGES[FTZ_ERR_ISSUER] = "issuer is not in issuers"
+
+
+class RequestSigners(ctypes.Structure):
+    """ftz_request_signers"""
+    _fields_ = [("ix", ctypes.c_void_p), ("ec", ctypes.c_void_p), ("auditor", ctypes.c_void_p),
+                ("auditor_len", ctypes.c_size_t), ("issuers", ctypes.POINTER(Bytes)), ("n_issuers", ctypes.c_size_t)]
+
+
+class SignedRequest(ctypes.Structure):
+    """ftz_signed_request"""
+    _fields_ = [("raw", Bytes), ("binding", Bytes)]
+
+
+def pack_signed_requests(requests, bindings):
+    """-> (ftz_signed_request array, keepalive)"""
+    requests, bindings = list(requests), list(bindings)
+    if len(requests) != len(bindings):
+        raise ValueError("one binding per request")
+    ra, rk = pack_bytes(requests)
+    ba, bk = pack_bytes([b.encode() if isinstance(b, str) else b for b in bindings])
+    arr = (SignedRequest * max(1, len(requests)))()
+    for k in range(len(requests)):
+        arr[k].raw, arr[k].binding = ra[k], ba[k]
+    return arr, (rk, bk)
 
 
 class PsSig(ctypes.Structure):
@@ -430,6 +456,7 @@ SYMBOLS = ["ftz_options_default", "ftz_ctx_create", "ftz_ctx_create_ex", "ftz_ct
            "ftz_batch_run", "ftz_batch_submit", "ftz_batch_wait", "ftz_batch_codes", "ftz_batch_bitmap", "ftz_batch_stats", "ftz_batch_size",
            "ftz_batch_destroy", "ftz_batch_challenges", "ftz_msm_g1", "ftz_msm_load", "ftz_msm_load_gen", "ftz_msm_run", "ftz_msm_set_scalars", "ftz_msm_run_scalars", "ftz_host_alloc", "ftz_host_free", "ftz_msm_info", "ftz_msm_destroy", "ftz_g1_sum",
            "ftz_token_request_decode", "ftz_verify_token_requests", "ftz_verify_token_requests_batched", "ftz_ctx_request_stats",
+           "ftz_verify_signed_token_requests",
            "ftz_idemix_create", "ftz_verify_owner_signatures", "ftz_idemix_set_strict_nym", "ftz_idemix_destroy", "ftz_audit_owners",
            "ftz_idemix_add_signer", "ftz_sign_owner_signatures", "ftz_idemix_make_nyms",
            "ftz_ecdsa_create", "ftz_ecdsa_add_identity", "ftz_verify_ecdsa_signatures", "ftz_x509_public_key", "ftz_ecdsa_destroy",
@@ -548,6 +575,9 @@ def load():
     lib.ftz_verify_token_requests_batched.argtypes = [vp, sz, ctypes.POINTER(Bytes), vp, vp,
                                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     lib.ftz_ctx_request_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+    lib.ftz_verify_signed_token_requests.argtypes = [vp, ctypes.POINTER(RequestSigners), sz,
+                                                     ctypes.POINTER(SignedRequest), vp, vp,
+                                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     szp = ctypes.POINTER(ctypes.c_size_t)
     i32p = ctypes.POINTER(ctypes.c_int32)
     lib.ftz_prove_transfers.argtypes = [vp, sz, ctypes.POINTER(TransferWitness), u8p, sz, szp, i32p]

@@ -545,7 +545,8 @@ int ftz_idemix_make_nyms(ftz_idemix* ix, int32_t signer, size_t n, const uint8_t
  * as in the reference; Go's x509.ParseCertificate is stricter than the walk to
  * the key done here, so register only identities the Go deserializer has
  * accepted (for the auditor and issuers: when the public parameters load).
- * Not wired into ftz_verify_token_requests. */
+ * ftz_verify_signed_token_requests (below) runs these checks inside the request
+ * path; ftz_verify_token_requests does not. */
 #define FTZ_ERR_IDENTITY 13 /* the identity does not deserialize to an ECDSA public key */
 typedef struct ftz_ecdsa ftz_ecdsa;
 typedef struct {
@@ -606,6 +607,69 @@ int ftz_ecdsa_add_signer(ftz_ecdsa* e, const uint8_t d[32], int32_t* signer, uin
 int ftz_sign_ecdsa(ftz_ecdsa* e, size_t n, const ftz_ecdsa_sign_item* it, uint8_t* sigs, uint32_t* sig_lens,
                    int32_t* codes);
 void ftz_ecdsa_destroy(ftz_ecdsa* e);
+
+/* ---- token requests with their signatures: Validator.VerifyTokenRequestFromRaw
+ * (crypto/validator/validator.go:45-108) with the auditor's, the issuers' and
+ * the owners' signatures beside the proofs; HTLC scripts and metadata counting
+ * stay in Go.  One verdict per request: the first check that fails in the
+ * reference's order.
+ *
+ * Signed message of a request: asn1.Marshal(TokenRequest{Issues, Transfers}) ||
+ * binding (validator.go:57-66) -- the first two fields of `raw` as they stand
+ * (the decoder accepts minimal DER only) under a recomputed outer header,
+ * followed by 30 00 30 00 for the two nil slices; trailing bytes and extra
+ * fields of `raw` never enter it.  Signature list (common/backend.go:32-40):
+ * AuditorSignatures ++ Signatures when len(auditor) != 0, else Signatures; each
+ * check below consumes the next one, a check that finds the list exhausted
+ * fails with FTZ_ERR_SIGNATURE, left-over signatures are ignored.
+ *
+ *   1  empty request, ASN.1 (:46-53)                              FTZ_ERR_PARSE, -1
+ *   2  auditor != NULL: its identity decodes (:136-139), the next signature
+ *      verifies (:141)            FTZ_ERR_IDENTITY / _UNSUPPORTED / _SIGNATURE, -1
+ *   3  every issue action, then every transfer action, unmarshals (:83-90)
+ *                                                                 FTZ_ERR_PARSE, -1
+ *   4  issue k: the proof checks of ftz_verify_token_requests (:151)
+ *   5  issue k: Issuer is byte-equal to one of `issuers`, if any (:155-168)
+ *                                                                 FTZ_ERR_ISSUER
+ *   6  issue k: the issuer's identity decodes, the next signature verifies
+ *      (:170-176)                 FTZ_ERR_IDENTITY / _UNSUPPORTED / _SIGNATURE
+ *   7  transfer t, input j (validator_transfer.go:50-76): the state loads and is
+ *      a token.Token                                              FTZ_ERR_INPUT
+ *   8  the same input: its Owner gives a verifier
+ *                                   FTZ_ERR_OWNER; a script owner FTZ_ERR_UNSUPPORTED
+ *   9  the same input: the next signature verifies                FTZ_ERR_SIGNATURE
+ *  10  transfer t: the proof checks of ftz_verify_token_requests
+ *
+ * Rows 4-6 are finished for issue k before issue k + 1; rows 7-9 run per input,
+ * all inputs of a transfer before its proof.  A non-NULL auditor of length 0 is
+ * Go's empty non-nil slice: row 2 runs and fails with FTZ_ERR_IDENTITY.
+ * FTZ_ERR_UNSUPPORTED takes its place in the order like a failure and means
+ * "hand this request to Go".  failed_action as for ftz_verify_token_requests.
+ *
+ * The auditor and every issuers[i] are registered on `ec` with
+ * ftz_ecdsa_add_identity on first use (more than 64 keys on the handle:
+ * FTZ_E_INVALID for the call; an identity the handle cannot decode or does not
+ * support fails only the requests that need it).  With n_issuers = 0 an issuer
+ * is decoded per item.  All proof and signature checks of a pipeline chunk run
+ * side by side, the signatures on the handles' own streams; the verdicts are
+ * merged on the host.  Thread-safe like ftz_verify_token_requests_batched;
+ * get_states is called under the same rules. */
+#define FTZ_ERR_ISSUER 15 /* an issue action's Issuer is not among the public parameters' Issuers */
+typedef struct {
+  ftz_idemix* ix;            /* owner signatures; NULL: any transfer input is FTZ_ERR_UNSUPPORTED */
+  ftz_ecdsa* ec;             /* auditor / issuer signatures; NULL likewise for those               */
+  const uint8_t* auditor;    /* PublicParams.Auditor; NULL = nil (no auditor check).  Non-NULL with */
+  size_t auditor_len;        /* length 0 = Go's empty non-nil slice (row 2 fails)                   */
+  const ftz_bytes* issuers;  /* PublicParams.Issuers; n_issuers = 0: any issuer is admitted         */
+  size_t n_issuers;
+} ftz_request_signers;
+typedef struct {
+  ftz_bytes raw;
+  ftz_bytes binding; /* the txID string */
+} ftz_signed_request;
+int ftz_verify_signed_token_requests(ftz_ctx* ctx, const ftz_request_signers* signers, size_t n,
+                                     const ftz_signed_request* reqs, ftz_get_states_fn get_states, void* user,
+                                     int32_t* codes, int32_t* failed_action);
 
 /* ---- standalone BN254 G1 multi-scalar multiplication (BASELINE configs[2]):
  * out = sum_i k_i P_i as 64-byte gnark RawBytes.  Points: n x 64-byte
