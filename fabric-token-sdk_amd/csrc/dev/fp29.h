@@ -53,6 +53,17 @@ FTS_HD int32_t pin32(int32_t x) {
 }
 static constexpr int32_t F29_MASK = (1 << 29) - 1;
 
+// c in any active lane of the wave (a ballot: the branch on it is uniform, so a
+// step no lane needs is skipped and not merely masked); the host build, one
+// lane at a time, takes the same branch per lane
+FTS_HD bool wave_any(bool c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ballot_w64(c) != 0;
+#else
+  return c;
+#endif
+}
+
 FTS_HD void pin29(f29& a) {
 #pragma unroll
   for (int i = 0; i < 9; i++) a.l[i] = pin32(a.l[i]);
@@ -607,12 +618,17 @@ FTS_HD j29 j29_dbl(const j29& p) {
 // 8M + 3S in ten reductions.  The exceptional cases are caught after the fact:
 // Z3 = Z1 H (|Z3| < p) vanishes iff H does, and then the sum is infinity
 // (r != 0) or a doubling (r == 0, p == (x2, y2)).
-FTS_HD j29 j29_madd(const j29& p, const f29& x2, const f29& y2) {
+// j29_madd_h also hands out H (Hout: unreduced, (3.11, 3), a multiplicand only):
+// Z3 = Z1 H, so along a run of additions the H are the ratios of the Z (the
+// window table of dev/jobs.h g1_mul_glv16_j29 is normalised with them).  Not
+// written when p is infinity.
+FTS_HD j29 j29_madd_h(const j29& p, const f29& x2, const f29& y2, f29& Hout) {
   if (p.inf) return {f29_breduce(x2), f29_breduce(y2), f29_breduce(f29_from_fp(fe_one<ModP>())), false};
   const f29 Z1Z1 = s29_sqr(p.z);                           // (0.54, 1)
   const f29 U2 = s29_mul(x2, Z1Z1);                        // 32 x 0.54 / 169 + 0.5: (0.61, 1)
   const f29 S2 = s29_mul(y2, s29_mul(p.z, Z1Z1));          // (0.61, 1)
   const f29 H = f29_sub(U2, p.x);                          // (3.11, 3)
+  Hout = H;
   const f29 Z3 = s29_mul(p.z, H);                          // 7.8 / 169 + 0.5: (0.55, 1), column 6 + 1
   const f29 rr = f29_sub(S2, p.y);                         // (3.11, 3)
   const f29 HH = s29_sqr(H);                               // (0.56, 1), column 9 + 1
@@ -627,6 +643,10 @@ FTS_HD j29 j29_madd(const j29& p, const f29& x2, const f29& y2) {
     return o;
   }
   return {X3, Y3, Z3, false};
+}
+FTS_HD j29 j29_madd(const j29& p, const f29& x2, const f29& y2) {
+  f29 H;
+  return j29_madd_h(p, x2, y2, H);
 }
 
 // add-2007-bl full Jacobian addition p + q: 11M + 5S, inputs normalised with

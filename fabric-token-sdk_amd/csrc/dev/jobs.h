@@ -604,13 +604,15 @@ FTS_HD int booth16(const uint32_t k[4], int i) {
 // (X_e s_e^2, Y_e s_e^3), s_e = Zc / Z_e, of the isomorphic curve
 // y^2 = x^3 + b Zc^6 (the a = 0 doubling and mixed-addition formulas do not
 // involve b), and the result (X:Y:Z) there is (X:Y:Z Zc) on E.
-FTS_HD void g1dev_put(G1Dev& d, const fp& a, const fp& b) {
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    d.x[q] = a.v[q];
-    d.y[q] = b.v[q];
-  }
-}
+//
+// The whole chain runs in the balanced 29-bit form (dev/fp29.h): the input
+// point, the input Z and the result are the only conversions.  A table entry is
+// (x, y, beta x) in limbs, written once by the build and read by the window
+// loop as it is: no repack and no beta product per window.
+struct G1Tab29 {
+  int32_t x[9], y[9], bx[9];
+};
+// the two field elements of a G1Dev as they lie (no infinity test)
 FTS_HD void g1dev_get(const G1Dev& d, fp& a, fp& b) {
 #pragma unroll
   for (int q = 0; q < 8; q++) {
@@ -618,83 +620,158 @@ FTS_HD void g1dev_get(const G1Dev& d, fp& a, fp& b) {
     b.v[q] = d.y[q];
   }
 }
-// tb: 16 G1Dev entries at stride st (device: a per-batch buffer laid out
-// [entry][job] so that a wave's accesses coalesce; host: a local array).
-// Entries 0..7 hold the table, 8..15 the (Z, prefix) pairs while it is built.
-// g1_mul_glv16_iso: k V for V = (X:Y:Z) Jacobian on E, Z != 0, without
-// bringing V to affine first: (X, Y) is an affine point of the isomorphic curve
-// y^2 = x^3 + b Z^6 (psi(x, y) = (x Z^2, y Z^3) maps E onto it and commutes with
-// negation and phi(x, y) = (beta x, y)), so the same code runs on (X, Y) and
-// the result (X':Y':Z') there is (X':Y':Z' Z) on E -- one product for an
-// inversion.
-FTS_HD g1j g1_mul_glv16_iso(const g1a& p, const fp& zin, const uint32_t k[8], G1Dev* tb, size_t st);
-FTS_HD g1j g1_mul_glv16(const g1a& p, const uint32_t k[8], G1Dev* tb, size_t st) {
-  if (p.inf) return jac_inf<fp>();
-  return g1_mul_glv16_iso(p, fe_one<ModP>(), k, tb, st);
+static constexpr int G1VTAB_ENTRIES = 8;  // per chain; the batch buffer is laid out [entry][job]
+static_assert(G1VTAB_ENTRIES * sizeof(G1Tab29) <= 16 * sizeof(G1Dev), "the window table grew past its earlier size");
+FTS_HD f29 f29_ld(const int32_t* w) {
+  f29 r;
+#pragma unroll
+  for (int q = 0; q < 9; q++) r.l[q] = w[q];
+  return r;
 }
-// The window loop on given halves: (-1)^n1 k1 V + (-1)^n2 k2 phi(V) for any
-// k1, k2 < 2^128 (glv_split's stay below 2^127, so a test that wants the top
-// window's digit or a chosen digit pattern calls this).
-FTS_HD g1j g1_mul_glv16_halves(const g1a& p, const fp& zin, const uint32_t k1[4], bool n1, const uint32_t k2[4],
-                               bool n2, G1Dev* tb, size_t st);
-FTS_HD g1j g1_mul_glv16_iso(const g1a& p, const fp& zin, const uint32_t k[8], G1Dev* tb, size_t st) {
+FTS_HD void f29_st(int32_t* w, const f29& a) {
+#pragma unroll
+  for (int q = 0; q < 9; q++) w[q] = a.l[q];
+}
+// entry (X s^2, Y s^3) of the common-Z table from the Jacobian (X, Y) and
+// s = Zc / Z, with beta x beside it.  X, Y: j29 outputs (|X| <= 2.1 p), s a
+// reduced product (0.56, 1) or an H of j29_madd_h (3.11, 3): s2 (0.56, 1),
+// s3 <= 3.11 x 0.56 / 169 + 0.5 = (0.52, 1), x, y, beta x (0.51, 1) -- inside
+// j29_madd's bounds for the affine operand (B <= 32, |limb| < 2^29), negated or not.
+FTS_HD void g1tab29_put(G1Tab29& t, const f29& X, const f29& Y, const f29& s, const f29& beta) {
+  const f29 s2 = s29_sqr(s);
+  const f29 x = s29_mul(X, s2);
+  f29_st(t.x, x);
+  f29_st(t.y, s29_mul(Y, s29_mul(s, s2)));
+  f29_st(t.bx, s29_mul(x, beta));
+}
+// tb: G1VTAB_ENTRIES entries at stride st (device: a per-batch buffer laid out
+// [entry][job] so that a wave's accesses coalesce; host: a local array).
+// g1_mul_glv16_j29: (-1)^n1 k1 V + (-1)^n2 k2 phi(V) for V = (X:Y:Z) Jacobian on
+// E, Z != 0 and any k1, k2 < 2^128, without bringing V to affine first: (X, Y)
+// is an affine point of the isomorphic curve y^2 = x^3 + b Z^6
+// (psi(x, y) = (x Z^2, y Z^3) maps E onto it and commutes with negation and
+// phi(x, y) = (beta x, y)), so the same code runs on (X, Y) and the result
+// (X':Y':Z') there is (X':Y':Z' Z) on E -- one product for an inversion.
+// V's coordinates: j29 outputs or balanced reductions (|X|, |Y| <= 2.1 p,
+// |Z| <= 0.56 p, L = 1).
+//
+// Table: T_0 = P1 = (X, Y) with Z_0 = 1, T_1 = 2 P1 (j29_dbl), T_e = T_(e-1) +
+// P1 (j29_madd_h, e = 2..7; for a point of order r none of them is
+// exceptional).  The addition's Z3 = Z1 H makes Z_7 = Z_e H_e ... H_6, so with
+// the common Z chosen as Zc = Z_7 the factor s_e = Zc / Z_e is the suffix
+// product H_e ... H_6 (s_7 = 1, s_0 = Z_7): entry e waits in the table as
+// (X_e, Y_e, H_e) and is normalised on the way back, five suffix products and
+// four products an entry, all scanned (s29_*).  The signs of the halves are
+// applied in the window loop, with the digits' signs.
+//
+// g1_vtab29_build writes the table of V and returns Zc Z, the factor that
+// brings the chain's result back to E; it does not depend on the scalar, so
+// the halves are split only after it (eight registers fewer across the build,
+// which is where the kernel's register demand peaks).
+FTS_HD f29 g1_vtab29_build(const j29& V, G1Tab29* tb, size_t st) {
+  // constants in f29_reduce's unsigned limbs ((1.5, 2): they fold at compile time)
+  const f29 one = f29_reduce(f29_from_fp(fe_one<ModP>()));
+  const f29 beta = f29_reduce(f29_from_fp(fe_const<ModP>(GLV_BETA)));
+  f29_st(tb[0].bx, V.z);  // waits in a slot the build leaves free, not in registers
+  j29 T = j29_dbl(j29{V.x, V.y, one, false});
+#pragma nounroll
+  for (int e = 1; e < 7; e++) {
+    G1Tab29& t = tb[e * st];
+    f29_st(t.x, T.x);
+    f29_st(t.y, T.y);
+    f29 H;
+    T = j29_madd_h(T, V.x, V.y, H);
+    f29_st(t.bx, H);
+  }
+  {  // s_7 = 1: |X_7| <= 2.1 p, |Y_7| <= 0.56 p are entries as they are
+    G1Tab29& t = tb[7 * st];
+    f29_st(t.x, T.x);
+    f29_st(t.y, T.y);
+    f29_st(t.bx, s29_mul(T.x, beta));
+  }
+  const f29 Zf = s29_mul(T.z, f29_ld(tb[0].bx));  // (0.51, 1)
+  g1tab29_put(tb[0], V.x, V.y, T.z, beta);
+  f29 suf = f29_ld(tb[6 * st].bx);  // s_6 = H_6, unreduced
+#pragma nounroll
+  for (int e = 6;;) {
+    G1Tab29& t = tb[e * st];
+    g1tab29_put(t, f29_ld(t.x), f29_ld(t.y), suf, beta);
+    if (--e == 0) break;
+    suf = s29_mul(suf, f29_ld(tb[e * st].bx));  // at most 3.11^2 / 169 + 0.5: (0.56, 1), column 9 + 1
+  }
+  return Zf;
+}
+// The window loop over the table of V: (-1)^n1 k1 V + (-1)^n2 k2 phi(V).  The
+// signs of the halves and of the digits are negations of y.
+FTS_HD g1j g1_vtab29_chain(const uint32_t k1[4], bool n1, const uint32_t k2[4], bool n2, const G1Tab29* tb, size_t st,
+                           const f29& Zf) {
+  j29 a = {f29{}, f29{}, f29{}, true};
+  // 33 windows from the top.  A step that no active lane of the wave needs is
+  // skipped: the doublings while every accumulator is still at infinity, an
+  // addition whose digit is zero in every lane (window 32 of glv_split's halves,
+  // which stay below 2^127 in practice, and with it window 31's doublings).  A
+  // lane whose digit is not zero computes what it always did.  The body holds
+  // ONE doubling and ONE addition, looped (four doublings, the two halves): about
+  // 31 KB of code against 85 KB with the six written out, the same instructions
+  // issued, and measured faster (profiles/r11/README.md; a compute unit pair's
+  // instruction cache is 64 KB on CDNA3, which the longer body would not fit).
+#pragma nounroll
+  for (int i = 32; i >= 0; i--) {
+    const int d1 = booth16(k1, i), d2 = booth16(k2, i);
+    const int m1 = d1 < 0 ? -d1 : d1, m2 = d2 < 0 ? -d2 : d2;
+    if (wave_any(!a.inf)) {
+#pragma nounroll
+      for (int q = 0; q < 4; q++) a = j29_dbl(a);
+    }
+#pragma nounroll
+    for (int h = 0; h < 2; h++) {
+      const int d = h ? d2 : d1, m = h ? m2 : m1;
+      if (wave_any(m != 0)) {
+        const G1Tab29& t = tb[(size_t)(m ? m - 1 : 0) * st];
+        const f29 y = f29_ld(t.y);
+        const j29 na = j29_madd(a, f29_ld(h ? t.bx : t.x), ((d < 0) != (h ? n2 : n1)) ? f29_neg(y) : y);
+        if (m) a = na;
+      }
+    }
+  }
+  if (a.inf) return jac_inf<fp>();
+  a.z = s29_mul(a.z, Zf);  // back to E
+  return j29_to(a);
+}
+FTS_HD g1j g1_mul_glv16_j29(const j29& V, const uint32_t k1[4], bool n1, const uint32_t k2[4], bool n2, G1Tab29* tb,
+                            size_t st) {
+  const f29 Zf = g1_vtab29_build(V, tb, st);
+  return g1_vtab29_chain(k1, n1, k2, n2, tb, st, Zf);
+}
+FTS_HD g1j g1_mul_glv16_iso(const j29& V, const uint32_t k[8], G1Tab29* tb, size_t st) {
+  const f29 Zf = g1_vtab29_build(V, tb, st);
   uint32_t k1[4], k2[4];
   bool n1, n2;
   glv_split(k, k1, n1, k2, n2);
-  return g1_mul_glv16_halves(p, zin, k1, n1, k2, n2, tb, st);
+  return g1_vtab29_chain(k1, n1, k2, n2, tb, st, Zf);
+}
+// The same from the 32-bit form: p = (X, Y) and zin = Z of V (glv_split's
+// halves stay below 2^127, so a test that wants the top window's digit or a
+// chosen digit pattern calls the halves entry).
+FTS_HD j29 j29_from_xyz(const fp& x, const fp& y, const fp& z) {
+  return {f29_breduce(f29_from_fp(x)), f29_breduce(f29_from_fp(y)), f29_breduce(f29_from_fp(z)), false};
 }
 FTS_HD g1j g1_mul_glv16_halves(const g1a& p, const fp& zin, const uint32_t k1[4], bool n1, const uint32_t k2[4],
+                               bool n2, G1Tab29* tb, size_t st) {
+  return g1_mul_glv16_j29(j29_from_xyz(p.x, p.y, zin), k1, n1, k2, n2, tb, st);
+}
+FTS_HD g1j g1_mul_glv16(const g1a& p, const uint32_t k[8], G1Tab29* tb, size_t st) {
+  if (p.inf) return jac_inf<fp>();
+  return g1_mul_glv16_iso(j29_from_xyz(p.x, p.y, fe_one<ModP>()), k, tb, st);
+}
+// Callers that keep the table's storage as the 16 G1Dev it once took (host
+// code with a local array): the entries lie in its first 864 bytes.
+FTS_HD g1j g1_mul_glv16_halves(const g1a& p, const fp& zin, const uint32_t k1[4], bool n1, const uint32_t k2[4],
                                bool n2, G1Dev* tb, size_t st) {
-  g1j acc = jac_inf<fp>();
-  g1a P1 = n1 ? aff_neg(p) : p;
-  g1j T = jac_from_aff(P1);
-  fp pre = fe_one<ModP>();
-#pragma nounroll
-  for (int e = 0; e < 8; e++) {
-    if (e == 1) T = jac_dbl(T);
-    if (e >= 2) T = jac_add_aff(T, P1);
-    g1dev_put(tb[e * st], T.x, T.y);
-    g1dev_put(tb[(8 + e) * st], T.z, pre);
-    pre = pre * T.z;
-  }
-  const fp Zc = pre;
-  fp suf = fe_one<ModP>();
-#pragma nounroll
-  for (int e = 7; e >= 0; e--) {
-    fp X, Y, Z, pe;
-    g1dev_get(tb[e * st], X, Y);
-    g1dev_get(tb[(8 + e) * st], Z, pe);
-    fp se = pe * suf;
-    fp s2 = sqr(se);
-    suf = suf * Z;
-    g1dev_put(tb[e * st], X * s2, Y * (s2 * se));
-  }
-  const bool flip = n1 != n2;  // phi(e P1) = +-phi(e p): sign of the second half
-  const f29 beta29 = f29_reduce(f29_from_fp(fe_const<ModP>(GLV_BETA)));
-  j29 a = {f29{}, f29{}, f29{}, true};
-#pragma nounroll
-  for (int i = 32; i >= 0; i--) {
-    int d1 = booth16(k1, i), d2 = booth16(k2, i);
-    int m1 = d1 < 0 ? -d1 : d1, m2 = d2 < 0 ? -d2 : d2;
-    fp x1, y1, x2, y2;
-    g1dev_get(tb[(size_t)(m1 ? m1 - 1 : 0) * st], x1, y1);
-    g1dev_get(tb[(size_t)(m2 ? m2 - 1 : 0) * st], x2, y2);
-    if (i != 32) {
-      a = j29_dbl(a);
-      a = j29_dbl(a);
-      a = j29_dbl(a);
-      a = j29_dbl(a);
-    }
-    f29 Y = f29_from_fp(y1);
-    j29 na = j29_madd(a, f29_from_fp(x1), (d1 < 0) ? f29_neg(Y) : Y);
-    if (m1) a = na;
-    Y = f29_from_fp(y2);
-    na = j29_madd(a, s29_mul(f29_from_fp(x2), beta29), ((d2 < 0) != flip) ? f29_neg(Y) : Y);
-    if (m2) a = na;
-  }
-  acc = j29_to(a);
-  acc.z = acc.z * (Zc * zin);  // back to E (the point at infinity keeps z = 0)
-  return acc;
+  return g1_mul_glv16_halves(p, zin, k1, n1, k2, n2, reinterpret_cast<G1Tab29*>(tb), st);
+}
+FTS_HD g1j g1_mul_glv16(const g1a& p, const uint32_t k[8], G1Dev* tb, size_t st) {
+  return g1_mul_glv16(p, k, reinterpret_cast<G1Tab29*>(tb), st);
 }
 
 FTS_HD void g1_emit_bytes(const G1Job& j, const g1a& r, uint8_t* arena) {
@@ -744,20 +821,41 @@ FTS_HD g1j g1j_load(const G1JDev& d) {
 //     left-to-right double-and-add over the c_t's bits (PP-A, b = 100, e = 2:
 //     6 doublings and 4 additions).
 FTS_HD uint64_t vterm_w(const VTerm& v) { return ((uint64_t)v.w_hi << 32) | v.w_lo; }
-FTS_HD g1j g1_var_point(const G1Job& j, const VTerm* vterms, const G1Dev* pts) {
+// V + (-1)^neg P for a proof point P as it lies in pts (all-zero: infinity),
+// by j29_madd with its exceptional cases (V at infinity, V = +-P); P's limbs
+// are f29_from_fp's (B <= 32, L = 1), inside j29_madd's bounds
+FTS_HD j29 g1_vadd29(const j29& V, const G1Dev& d, bool neg) {
+  const g1a P = g1_load(d);
+  if (P.inf) return V;
+  const f29 y = f29_from_fp(P.y);
+  return j29_madd(V, f29_from_fp(P.x), neg ? f29_neg(y) : y);
+}
+// a proof point as a Jacobian point with Z = 1, balanced (0.51, 1)
+FTS_HD j29 g1_vpoint29(const G1Dev& d) {
+  const g1a P = g1_load(d);
+  j29 V = j29_from_xyz(P.x, P.y, fe_one<ModP>());
+  V.inf = P.inf;
+  return V;
+}
+// The result is in the 29-bit form (j29_dbl / j29_madd outputs or balanced
+// reductions: |X| <= 2.1 p, |Y|, |Z| <= 0.56 p, L = 1), which is what
+// g1_mul_glv16_j29 takes.
+FTS_HD j29 g1_var_point(const G1Job& j, const VTerm* vterms, const G1Dev* pts) {
   const VTerm& v0 = vterms[j.vstart];
   const uint64_t b = vterm_w(v0);
   const bool horner = (v0.flags & VT_HORNER) != 0;
-  if (j.vcount == 1 && (horner || b == 1) && !(v0.flags & VT_NEG)) return jac_from_aff(g1_load(pts[v0.pt]));
+  if (j.vcount == 1 && (horner || b == 1) && !(v0.flags & VT_NEG)) return g1_vpoint29(pts[v0.pt]);
   if (horner && (b & (b - 1)) == 0) {
-    const int top = b ? 63 - __builtin_clzll(b) : 0;
-    g1j V = jac_from_aff(g1_load(pts[v0.pt]));
+    if (!b) return g1_vpoint29(pts[vterms[j.vstart + j.vcount - 1].pt]);
+    const int top = 63 - __builtin_clzll(b);
+    j29 V = g1_vpoint29(pts[v0.pt]);
+#pragma nounroll
     for (uint32_t t = 1; t < j.vcount; t++) {
 #pragma nounroll
-      for (int q = 0; q < top; q++) V = jac_dbl(V);
-      V = jac_add_aff(V, g1_load(pts[vterms[j.vstart + t].pt]));
+      for (int q = 0; q < top; q++) V = j29_dbl(V);
+      V = g1_vadd29(V, pts[vterms[j.vstart + t].pt], false);
     }
-    return b ? V : jac_from_aff(g1_load(pts[vterms[j.vstart + j.vcount - 1].pt]));
+    return V;
   }
   // joint double-and-add; term t's weight: horner b^(count-1-t), else w_t
   uint64_t cmax = 0;
@@ -767,21 +865,18 @@ FTS_HD g1j g1_var_point(const G1Job& j, const VTerm* vterms, const G1Dev* pts) {
   } else {
     for (uint32_t t = 0; t < j.vcount; t++) cmax |= vterm_w(vterms[j.vstart + t]);
   }
-  g1j V = jac_inf<fp>();
+  j29 V = {f29{}, f29{}, f29{}, true};
   if (cmax == 0) return V;
   const int top = 63 - __builtin_clzll(cmax);
 #pragma nounroll
   for (int q = top; q >= 0; q--) {
-    if (q != top) V = jac_dbl(V);
+    if (q != top) V = j29_dbl(V);
     uint64_t c = 1;
 #pragma nounroll
     for (uint32_t t = j.vcount; t-- > 0;) {
       const VTerm& vt = vterms[j.vstart + t];
       const uint64_t w = horner ? c : vterm_w(vt);
-      if ((w >> q) & 1) {
-        const g1a P = g1_load(pts[vt.pt]);
-        V = jac_add_aff(V, (vt.flags & VT_NEG) ? aff_neg(P) : P);
-      }
+      if ((w >> q) & 1) V = g1_vadd29(V, pts[vt.pt], (vt.flags & VT_NEG) != 0);
       c *= b;
     }
   }
@@ -794,10 +889,10 @@ FTS_HD void job_g1(const G1Job& j, const VTerm* vterms, const G1Dev* pts, const 
                    const G1Dev* tab, G1Dev* g1out, uint8_t* arena) {
   g1j acc = jac_inf<fp>();
   if (j.vscal != NONE) {
-    g1j V = g1_var_point(j, vterms, pts);
-    if (j.vneg) V = jac_neg(V);
-    G1Dev loc[16];
-    if (!is_zero(V.z)) acc = g1_mul_glv16_iso(g1a{V.x, V.y, false}, V.z, scal[j.vscal], loc, 1);
+    j29 V = g1_var_point(j, vterms, pts);
+    if (j.vneg) V.y = f29_neg(V.y);
+    G1Tab29 loc[G1VTAB_ENTRIES];
+    if (!V.inf) acc = g1_mul_glv16_iso(V, scal[j.vscal], loc, 1);
   }
   for (int f = 0; f < j.nfix; f++) acc = g1_fixed_acc(acc, tab, j.fbase[f], scal[j.fscal[f]]);
   g1a r = jac_to_aff(acc);
@@ -808,11 +903,12 @@ FTS_HD void job_g1(const G1Job& j, const VTerm* vterms, const G1Dev* pts, const 
 }
 
 // Part f of job jb (i = f n + jb): f < 3 the fixed-base term f, f = 3 the
-// variable term by GLV.  vtab: per-batch scratch of 16 n G1Dev entries for the
-// variable parts' window tables (device); the host emulation may pass nullptr
-// (a local table).
+// variable term by GLV.  vtab: per-batch scratch of G1VTAB_ENTRIES n G1Tab29
+// entries for the variable parts' window tables (device); the host emulation
+// may pass nullptr (a local table) or storage of any type that is at least
+// that large (untyped for that reason).
 FTS_HD void job_g1_part(const G1Job* jobs, uint32_t n, uint32_t i, const VTerm* vterms, const G1Dev* pts,
-                        const uint32_t (*scal)[8], const G1Dev* tab, G1JDev* part, G1Dev* vtab) {
+                        const uint32_t (*scal)[8], const G1Dev* tab, G1JDev* part, void* vtab) {
   uint32_t f = i / n, jb = i - f * n;
   const G1Job& j = jobs[jb];
   if (f == 3 && j.sh_count) return;  // the siblings' partials (job_g1_sum_parts)
@@ -820,17 +916,18 @@ FTS_HD void job_g1_part(const G1Job* jobs, uint32_t n, uint32_t i, const VTerm* 
   if (f < 3) {
     if (f < j.nfix) acc = g1_fixed_acc(acc, tab, j.fbase[f], scal[j.fscal[f]]);
   } else if (j.vscal != NONE) {
-    g1j V = g1_var_point(j, vterms, pts);
-    if (j.vneg) V = jac_neg(V);
+    j29 V = g1_var_point(j, vterms, pts);
+    if (j.vneg) V.y = f29_neg(V.y);
+    G1Tab29* const vt29 = static_cast<G1Tab29*>(vtab);
 #if defined(__HIP_DEVICE_COMPILE__)
-    G1Dev* tb = vtab + jb;
+    G1Tab29* tb = vt29 + jb;
     const size_t st = n;
 #else
-    G1Dev loc[16];
-    G1Dev* tb = vtab ? vtab + jb : loc;
-    const size_t st = vtab ? n : 1;
+    G1Tab29 loc[G1VTAB_ENTRIES];
+    G1Tab29* tb = vt29 ? vt29 + jb : loc;
+    const size_t st = vt29 ? n : 1;
 #endif
-    if (!is_zero(V.z)) acc = g1_mul_glv16_iso(g1a{V.x, V.y, false}, V.z, scal[j.vscal], tb, st);
+    if (!V.inf) acc = g1_mul_glv16_iso(V, scal[j.vscal], tb, st);
   }
   g1j_store(part[i], acc);
 }

@@ -19,7 +19,7 @@ using namespace fts;
 __global__ void __launch_bounds__(128) k_g1_part(const G1Job* jobs, uint32_t n, const uint32_t* flist, uint32_t nfl,
                                                  const uint32_t* vlist, uint32_t nvl, const VTerm* vt,
                                                  const G1Dev* pts, const uint32_t (*scal)[8], const G1Dev* tab,
-                                                 G1JDev* part, G1Dev* vtab) {
+                                                 G1JDev* part, G1Tab29* vtab) {
   const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x, vbase = (nfl + 63) & ~63u;
   uint32_t i;
   if (lane < vbase) {

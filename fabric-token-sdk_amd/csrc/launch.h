@@ -64,7 +64,7 @@ __global__ void k_pp_decode(const uint8_t* raw, const uint32_t* g1off, uint32_t 
                             uint32_t n2, G1Dev* g1, G2Dev* g2, uint8_t* g1bytes, uint8_t* g2bytes, uint8_t* ok);
 __global__ void k_g1_part(const G1Job* jobs, uint32_t n, const uint32_t* flist, uint32_t nfl, const uint32_t* vlist,
                           uint32_t nvl, const VTerm* vt, const G1Dev* pts, const uint32_t (*scal)[8], const G1Dev* tab,
-                          G1JDev* part, G1Dev* vtab);
+                          G1JDev* part, G1Tab29* vtab);
 // lanes of a k_g1_part launch: the fixed list padded to a whole wave, then the variable list
 static inline uint32_t g1_part_lanes(uint32_t nfl, uint32_t nvl) { return ((nfl + 63) & ~63u) + nvl; }
 __global__ void k_g1_combine(const G1Job* jobs, uint32_t n, const G1JDev* part, G1Dev* g1out, uint8_t* arena,

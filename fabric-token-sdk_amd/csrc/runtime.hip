@@ -447,8 +447,8 @@ static void scratch_layout(ftz_batch* b) {
   s.part1 = take(sizeof(G1JDev) * 4 * n_g1);
   s.part1p = take(sizeof(G1JDev) * 4 * n_g1p);
   s.part2 = take(sizeof(G2PartDev) * 4 * n_pr);
-  s.vtab1 = take(sizeof(G1Dev) * 16 * n_g1);
-  s.vtab1p = take(sizeof(G1Dev) * 16 * n_g1p);
+  s.vtab1 = take(sizeof(G1Tab29) * G1VTAB_ENTRIES * n_g1);
+  s.vtab1p = take(sizeof(G1Tab29) * G1VTAB_ENTRIES * n_g1p);
   s.hash_ok = take(f.cnt[PS_HMAIN]);
   s.hash_ok_pre = take(f.cnt[PS_HPRE]);
   s.codes = take(sizeof(int32_t) * b->n);
@@ -616,7 +616,7 @@ struct SlotPtrs {
   EvLineDev* lines2;
   G1JDev *part1, *part1p;
   G2PartDev* part2;
-  G1Dev *vtab1, *vtab1p;
+  G1Tab29 *vtab1, *vtab1p;
   int32_t* codes;
   uint32_t* bitmap;
   uint32_t n_dec, n_zr, n_sc, n_sc1, n_sp, n_rnd, n_em, n_b64, n_g1, n_g1p, n_g2, n_pr, n_hp, n_hm, n_tx, n_cp, n_cp2;
@@ -670,8 +670,8 @@ static SlotPtrs slot_ptrs(ftz_batch* b) {
   p.part1 = reinterpret_cast<G1JDev*>(s + l.part1);
   p.part1p = reinterpret_cast<G1JDev*>(s + l.part1p);
   p.part2 = reinterpret_cast<G2PartDev*>(s + l.part2);
-  p.vtab1 = reinterpret_cast<G1Dev*>(s + l.vtab1);
-  p.vtab1p = reinterpret_cast<G1Dev*>(s + l.vtab1p);
+  p.vtab1 = reinterpret_cast<G1Tab29*>(s + l.vtab1);
+  p.vtab1p = reinterpret_cast<G1Tab29*>(s + l.vtab1p);
   p.hash_ok = s + l.hash_ok;
   p.hash_ok_pre = s + l.hash_ok_pre;
   p.codes = reinterpret_cast<int32_t*>(s + l.codes);

@@ -151,3 +151,174 @@ extern "C" int ftz_devcheck_sha(int device, uint32_t n, uint32_t block, const ui
   (void)hipFree(dout);
   return -(int)e;
 }
+
+// ---- the variable-base G1 chain as the verifier runs it (tests/test_gpu_g1_chain.py):
+// k_g1_part and k_g1_combine themselves (k_g1.hip compiled into this tool) over
+// a job array the caller describes, and the window loop on chosen GLV halves
+// (g1_mul_glv16_halves: glv_split's own halves never reach the top window), both
+// with the per-batch window table laid out [entry][job] as the runtime's.  Each
+// returns the device's affine points and the host build's of the same code.
+#include "../k_g1.hip"
+
+static void dc_aff_words(uint32_t* out, const g1j& p) {
+  G1Dev d;
+  g1_store(d, jac_to_aff(p));
+  memcpy(out, &d, sizeof(d));
+}
+
+static constexpr uint32_t DC_CHAIN_IN = 34;  // X[8] Y[8] Z[8] (Montgomery words), k1[4], n1, k2[4], n2
+struct DcChainIn {
+  g1a p;
+  fp z;
+  uint32_t k1[4], k2[4];
+  bool n1, n2;
+};
+FTS_HD DcChainIn dc_chain_ld(const uint32_t* q) {
+  DcChainIn c;
+  c.p = {dc_ld8<fp>(q), dc_ld8<fp>(q + 8), false};
+  c.z = dc_ld8<fp>(q + 16);
+  for (int i = 0; i < 4; i++) {
+    c.k1[i] = q[24 + i];
+    c.k2[i] = q[29 + i];
+  }
+  c.n1 = q[28] != 0;
+  c.n2 = q[33] != 0;
+  return c;
+}
+__global__ void __launch_bounds__(128) k_devcheck_g1_chain(uint32_t n, const uint32_t* in, uint32_t* out,
+                                                           G1Tab29* vtab) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const DcChainIn c = dc_chain_ld(in + (size_t)j * DC_CHAIN_IN);
+  dc_stj(out + (size_t)j * 24, g1_mul_glv16_halves(c.p, c.z, c.k1, c.n1, c.k2, c.n2, vtab + j, n));
+}
+
+// n vectors of DC_CHAIN_IN words, one lane each in workgroups of 128 (k_g1_part's).
+// out: n x 32 words, the device's affine point (x[8] y[8], all-zero: infinity)
+// then the host's.
+extern "C" int ftz_devcheck_g1_chain(int device, uint32_t n, const uint32_t* in, uint32_t* out) {
+  if (n == 0 || n > 65536 || !in || !out) return -1000;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return -(int)e;
+  const size_t in_bytes = (size_t)n * DC_CHAIN_IN * 4, res_bytes = (size_t)n * 24 * 4;
+  uint32_t *din = nullptr, *dout = nullptr;
+  G1Tab29* dtab = nullptr;
+  uint32_t* res = new uint32_t[(size_t)n * 24];
+  if ((e = hipMalloc(&din, in_bytes)) == hipSuccess && (e = hipMalloc(&dout, res_bytes)) == hipSuccess &&
+      (e = hipMalloc(&dtab, sizeof(G1Tab29) * G1VTAB_ENTRIES * n)) == hipSuccess &&
+      (e = hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemset(dout, 0, res_bytes)) == hipSuccess) {
+    k_devcheck_g1_chain<<<(n + 127) / 128, 128>>>(n, din, dout, dtab);
+    if ((e = hipGetLastError()) == hipSuccess && (e = hipDeviceSynchronize()) == hipSuccess)
+      e = hipMemcpy(res, dout, res_bytes, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  (void)hipFree(dtab);
+  if (e == hipSuccess)
+    for (uint32_t j = 0; j < n; j++) {
+      const uint32_t* r = res + (size_t)j * 24;
+      dc_aff_words(out + (size_t)j * 32, g1j{dc_ld8<fp>(r), dc_ld8<fp>(r + 8), dc_ld8<fp>(r + 16)});
+      const DcChainIn c = dc_chain_ld(in + (size_t)j * DC_CHAIN_IN);
+      G1Tab29 loc[G1VTAB_ENTRIES];
+      dc_aff_words(out + (size_t)j * 32 + 16, g1_mul_glv16_halves(c.p, c.z, c.k1, c.n1, c.k2, c.n2, loc, 1));
+    }
+  delete[] res;
+  return -(int)e;
+}
+
+// n G1 jobs without fixed-base terms through k_g1_part + k_g1_combine.
+//   jobs:   n x 6 words: vstart, vcount, vscal (0xFFFFFFFF: no variable part), vneg, sh_first, sh_count
+//   vterms: n_vt x 4 words (VTerm);  pts: n_pts x 16 words (G1Dev);  scal: n_scal x 8 words (< r)
+// Every index is checked against its array before anything runs (-1000).
+// out: n x 32 words, the device's g1out entry of job j then job_g1's on the host.
+extern "C" int ftz_devcheck_g1_jobs(int device, uint32_t n, const uint32_t* jobs, uint32_t n_vt, const uint32_t* vterms,
+                                    uint32_t n_pts, const uint32_t* pts, uint32_t n_scal, const uint32_t* scal,
+                                    uint32_t* out) {
+  if (n == 0 || n > 65536 || n_vt > 65536 || n_pts > 65536 || n_scal > 65536 || !jobs || !vterms || !pts || !scal || !out)
+    return -1000;
+  G1Job* hj = new G1Job[n];
+  uint32_t* vlist = new uint32_t[n];
+  uint32_t nvl = 0;
+  bool ok = true;
+  for (uint32_t j = 0; j < n; j++) {
+    const uint32_t* q = jobs + (size_t)j * 6;
+    G1Job g{};
+    g.vstart = q[0];
+    g.vcount = q[1];
+    g.vscal = q[2];
+    g.vneg = q[3] ? 1u : 0u;
+    g.sh_first = q[4];
+    g.sh_count = q[5];
+    g.out = j;
+    g.bytes = g.b64 = NONE;
+    if (g.vscal != NONE) {
+      ok = ok && g.vscal < n_scal && g.vcount >= 1 && g.vstart <= n_vt && g.vcount <= n_vt - g.vstart;
+      if (g.sh_count) {  // earlier jobs that run their own chain
+        ok = ok && g.sh_first <= j && g.sh_count <= j - g.sh_first;
+        for (uint32_t s = 0; ok && s < g.sh_count; s++)
+          ok = hj[g.sh_first + s].vscal != NONE && hj[g.sh_first + s].sh_count == 0;
+      } else {
+        vlist[nvl++] = 3 * n + j;
+      }
+    } else {
+      ok = ok && g.sh_count == 0;
+    }
+    hj[j] = g;
+  }
+  for (uint32_t t = 0; t < n_vt; t++) ok = ok && vterms[4 * (size_t)t] < n_pts;
+  hipError_t e = hipSuccess;
+  if (ok) e = hipSetDevice(device);
+  G1Job* dj = nullptr;
+  uint32_t *dvl = nullptr, *dvt = nullptr, *dpts = nullptr, *dscal = nullptr;
+  G1JDev* dpart = nullptr;
+  G1Tab29* dtab = nullptr;
+  G1Dev *dg1 = nullptr, *dpn = nullptr;
+  G1Dev* res = new G1Dev[n];
+  if (ok && e == hipSuccess && (e = hipMalloc(&dj, sizeof(G1Job) * n)) == hipSuccess &&
+      (e = hipMalloc(&dvl, 4 * (size_t)n)) == hipSuccess && (e = hipMalloc(&dvt, 16 * (size_t)(n_vt + 1))) == hipSuccess &&
+      (e = hipMalloc(&dpts, 64 * (size_t)(n_pts + 1))) == hipSuccess &&
+      (e = hipMalloc(&dscal, 32 * (size_t)(n_scal + 1))) == hipSuccess &&
+      (e = hipMalloc(&dpart, sizeof(G1JDev) * 4 * n)) == hipSuccess &&
+      (e = hipMalloc(&dtab, sizeof(G1Tab29) * G1VTAB_ENTRIES * n)) == hipSuccess &&
+      (e = hipMalloc(&dg1, sizeof(G1Dev) * n)) == hipSuccess && (e = hipMalloc(&dpn, sizeof(G1Dev) * n)) == hipSuccess &&
+      (e = hipMemcpy(dj, hj, sizeof(G1Job) * n, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dvl, vlist, 4 * (size_t)n, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dvt, vterms, 16 * (size_t)n_vt, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dpts, pts, 64 * (size_t)n_pts, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dscal, scal, 32 * (size_t)n_scal, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemset(dpart, 0, sizeof(G1JDev) * 4 * n)) == hipSuccess &&
+      (e = hipMemset(dg1, 0xA5, sizeof(G1Dev) * n)) == hipSuccess) {
+    if (const uint32_t lanes = g1_part_lanes(0, nvl))
+      k_g1_part<<<(lanes + 127) / 128, 128>>>(dj, n, nullptr, 0, dvl, nvl, reinterpret_cast<const VTerm*>(dvt),
+                                             reinterpret_cast<const G1Dev*>(dpts),
+                                             reinterpret_cast<const uint32_t(*)[8]>(dscal), nullptr, dpart, dtab);
+    k_g1_combine<<<(n + COMBINE_NT - 1) / COMBINE_NT, COMBINE_NT>>>(dj, n, dpart, dg1, nullptr, dpn);
+    if ((e = hipGetLastError()) == hipSuccess && (e = hipDeviceSynchronize()) == hipSuccess)
+      e = hipMemcpy(res, dg1, sizeof(G1Dev) * n, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dj);
+  (void)hipFree(dvl);
+  (void)hipFree(dvt);
+  (void)hipFree(dpts);
+  (void)hipFree(dscal);
+  (void)hipFree(dpart);
+  (void)hipFree(dtab);
+  (void)hipFree(dg1);
+  (void)hipFree(dpn);
+  if (ok && e == hipSuccess) {
+    G1Dev* host = new G1Dev[n];
+    for (uint32_t j = 0; j < n; j++)
+      job_g1(hj[j], reinterpret_cast<const VTerm*>(vterms), reinterpret_cast<const G1Dev*>(pts),
+             reinterpret_cast<const uint32_t(*)[8]>(scal), nullptr, host, nullptr);
+    for (uint32_t j = 0; j < n; j++) {
+      memcpy(out + (size_t)j * 32, &res[j], 64);
+      memcpy(out + (size_t)j * 32 + 16, &host[j], 64);
+    }
+    delete[] host;
+  }
+  delete[] res;
+  delete[] vlist;
+  delete[] hj;
+  return ok ? -(int)e : -1000;
+}
