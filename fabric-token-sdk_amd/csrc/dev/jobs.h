@@ -170,9 +170,19 @@ struct EmitJob {
   uint32_t src;   // EM_ZR: scalar index; EM_G1: arena offset of 64 RawBytes
 };
 // prover output: base64 of an inner JSON document into the outer proof
+// The generating calls (ftz_generate_*) add one emission level: their outer
+// proof is written into the arena (B64_TO_ARENA) and a second launch (B64_L2)
+// encodes it into the action's Proof hole and copies the finished pieces of the
+// action and metadata documents (B64_RAW) from the arena into the output.
+enum B64Flag : uint32_t {
+  B64_RAW = 0x80000000u,       // copy the bytes instead of encoding them
+  B64_TO_ARENA = 0x40000000u,  // dst is an arena offset
+  B64_L2 = 0x20000000u,        // runs in the second launch (reads what the first wrote)
+  B64_LEN = 0x1FFFFFFFu,
+};
 struct B64Job {
-  uint32_t src, len;  // arena range
-  uint32_t dst;       // offset in the proof output buffer
+  uint32_t src, len;  // arena range; len carries the B64Flag bits
+  uint32_t dst;       // offset in the proof output buffer (the arena with B64_TO_ARENA)
 };
 // prover: bytes the host does not write into the arena / proof output (a shape
 // template's image, then the witness bytes patched over it), copied on the
@@ -1049,6 +1059,20 @@ FTS_HD void job_rand(const RandJob& j, const uint8_t* arena, uint32_t (*scal)[8]
 // prover: byte b of a CopyJob (k_copy: one workgroup per job, lanes stride the bytes)
 FTS_HD void job_copy_byte(const CopyJob& j, uint32_t b, const uint8_t* wire, uint8_t* arena, uint8_t* out) {
   (j.to_out ? out : arena)[j.dst + b] = wire[j.src + b];
+}
+
+// prover output: unit u of a B64Job (k_b64: one workgroup per job, lanes stride
+// the units) -- a 3-byte group of an encoding job, a byte of a B64_RAW copy
+FTS_HD uint32_t job_b64_units(const B64Job& j) {
+  const uint32_t n = j.len & B64_LEN;
+  return (j.len & B64_RAW) ? n : (n + 2) / 3;
+}
+FTS_HD void job_b64_unit(const B64Job& j, uint32_t u, uint8_t* arena, uint8_t* out) {
+  uint8_t* d = ((j.len & B64_TO_ARENA) ? arena : out) + j.dst;
+  if (j.len & B64_RAW)
+    d[u] = arena[j.src + u];
+  else
+    b64_group(d + 4 * u, arena + j.src, j.len & B64_LEN, u);
 }
 
 // prover output holes (EmitJob): base64 of a 32-byte big-endian scalar or of

@@ -52,6 +52,7 @@ void Plan::clear() {
   out.clear();
   out_off.clear();
   item_off.clear();
+  gen_len.clear();
   g1fl.clear();
   g1vl.clear();
   g1pfl.clear();
@@ -1347,7 +1348,7 @@ void relocate_into(const Plan& b, const PieceBase& o, bool p2_g1out, bool keep_c
   B64Job* bj = reinterpret_cast<B64Job*>(dst[PS_B64]) + o.sec[PS_B64];
   for (B64Job j : b.b64) {
     j.src += o_arena;
-    j.dst += o_out;
+    j.dst += (j.len & B64_TO_ARENA) ? o_arena : o_out;
     *bj++ = j;
   }
   const int cps[2] = {PS_CP, PS_CP2};

@@ -112,6 +112,10 @@ struct Plan {
   std::vector<uint8_t> out;       // outer proof JSON templates, concatenated
   std::vector<uint32_t> out_off;  // per proof: start in `out` (plus a final end)
   std::vector<uint32_t> item_off; // openings: arena offset of the 128-byte result (recomputed | decoded)
+  // generating plans (host only, not a section): per order its action length, then
+  // the length of each output's metadata document (an order's output block is
+  // action | metadata documents | n_out x 64 commitment bytes)
+  std::vector<uint32_t> gen_len;
   // flattened plans only (plan_unflatten): the work lists of g1 / g1p (g1_part_lists)
   std::vector<uint32_t> g1fl, g1vl, g1pfl, g1pvl;
   bool p2_g1out = false;          // PairJob.p2 indexes g1out (prover) instead of pts
@@ -287,5 +291,49 @@ std::string plan_prove_issues(const PPInfo& pp, size_t n, const IssueWit* w, Pla
 std::string plan_prove_items_transfers(const PPInfo& pp, size_t n, const TransferWit* wit, PlanWork& w,
                                        WorkPool& pool);
 std::string plan_prove_items_issues(const PPInfo& pp, size_t n, const IssueWit* wit, PlanWork& w, WorkPool& pool);
+
+// ------------------------------------------------------------------ generating calls
+// An order of ftz_generate_transfers / ftz_generate_issues (Sender.GenerateZKTransfer,
+// crypto/transfer/sender.go:52-88; nonanonym Issuer.GenerateZKIssue,
+// crypto/issue/nonanonym/nonanonymissuer.go:37-80): the witness without output
+// commitments and output blinding factors -- the plan computes both -- plus the
+// strings the action and the metadata documents carry.
+struct GenBytes {
+  const uint8_t* p;  // null: Go nil (JSON null)
+  size_t len;
+};
+struct GenTransfer {
+  TransferWit w;           // outputs, out_bfs unused; out_values n_out x 32-byte big-endian
+  const GenBytes* ids;     // n_in ledger keys
+  const GenBytes* owners;  // n_out
+};
+struct GenIssue {
+  IssueWit w;  // outputs, bfs unused; anonymous 0
+  GenBytes issuer;
+  const GenBytes* owners;
+};
+// templates a planning piece keeps (orders with further distinct length tuples are planned directly)
+static constexpr size_t GEN_TPL_CAP = 32;
+// The refusals that need no planning: "" or "order i: ..." (no inputs / outputs,
+// null seed, exponent <= 0, a type or id that is not valid UTF-8)
+std::string gen_check(const PPInfo& pp, const GenTransfer& o, size_t idx);
+std::string gen_check(const PPInfo& pp, const GenIssue& o, size_t idx);
+// Byte lengths of an order's documents: len[0] the action, len[1 + k] output k's
+// metadata (n_out + 1 entries).  Lengths depend on the order's shape and string
+// lengths only; `cache` (opaque, may be shared by the orders of one call) keeps
+// the distinct shapes seen.  "" or an error text.
+struct GenSizeCache;
+GenSizeCache* gen_size_cache_new();
+void gen_size_cache_free(GenSizeCache*);
+std::string gen_sizes(const PPInfo& pp, const GenTransfer& o, size_t idx, GenSizeCache* cache, uint32_t* len);
+std::string gen_sizes(const PPInfo& pp, const GenIssue& o, size_t idx, GenSizeCache* cache, uint32_t* len);
+// Plans as plan_prove_* (merged form for the host emulation / piece form for the runtime's slots)
+std::string plan_gen_transfers(const PPInfo& pp, size_t n, const GenTransfer* o, Plan& out, int threads);
+std::string plan_gen_issues(const PPInfo& pp, size_t n, const GenIssue* o, Plan& out, int threads);
+std::string plan_gen_items_transfers(const PPInfo& pp, size_t n, const GenTransfer* o, PlanWork& w, WorkPool& pool);
+std::string plan_gen_items_issues(const PPInfo& pp, size_t n, const GenIssue* o, PlanWork& w, WorkPool& pool);
+// asn1.Marshal(driver.TokenRequest) (token/driver/request.go:24-38): minimal DER of
+// SEQUENCE { 4 x SEQUENCE OF OCTET STRING }.  Returns the length; writes when out != null.
+size_t der_encode_token_request(const GenBytes* const lists[4], const size_t counts[4], uint8_t* out);
 
 }  // namespace ftsh

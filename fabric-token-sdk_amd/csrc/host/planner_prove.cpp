@@ -9,6 +9,8 @@
 //                                         obfuscateSignature :196-222, computeCommitment :225-257
 //   issue.Prover.Prove / WF prover        issue/issue.go:151-184; issue/wellformedness.go:74-184
 //   token commitments                     token/token.go:64-98
+//   Sender.GenerateZKTransfer             transfer/sender.go:52-88      (plan_gen_*: the
+//   nonanonym Issuer.GenerateZKIssue      issue/nonanonym/nonanonymissuer.go:37-80   generating variants)
 // Randomness: the reference draws every blinding value from crypto/rand.  The
 // batch prover derives them from a per-proof 32-byte seed and a tag naming the
 // value, rand(tag) = SHA-256(seed||tag||0) || SHA-256(seed||tag||1) mod r, the
@@ -77,7 +79,9 @@ std::string go_json_str(const char* s, size_t n) {
 // on its shape.  Digit sources index k * e + i (token k, digit i).
 enum SrcKind : uint8_t {
   SRC_SEED, SRC_IN_PT, SRC_OUT_PT, SRC_IN_VAL, SRC_IN_BF, SRC_OUT_VAL, SRC_OUT_BF, SRC_TYPE,
-  SRC_SIG_R, SRC_SIG_S, SRC_DIGIT, SRC_NONE = 0xFF
+  SRC_SIG_R, SRC_SIG_S, SRC_DIGIT,
+  // generating calls: the escaped text of input id k, the bytes of owner k, of the issuer
+  SRC_ID, SRC_OWNER, SRC_ISSUER, SRC_NONE = 0xFF
 };
 struct Patch {
   uint8_t arena;  // 1: arena byte offset, 0: wire
@@ -249,6 +253,17 @@ struct PB {
     uint32_t pos, kind, src;
   };
   std::vector<Hole> holes;
+  // generating calls: base64 of arena bytes (owners, issuer) and witness text (ids)
+  // inside a document, as flags-carrying B64Jobs / arena patches
+  struct BHole {
+    uint32_t pos, src, len;
+  };
+  std::vector<BHole> bholes;
+  struct THole {
+    uint32_t pos, len, k;
+    uint8_t kind;
+  };
+  std::vector<THole> tholes;
   void lit(const char* s) { doc += s; }
   void zr(uint32_t scal) {
     doc += ZR_PRE;
@@ -274,9 +289,13 @@ struct PB {
   std::pair<uint32_t, uint32_t> flush_doc() {
     uint32_t off = arena_put(doc.data(), doc.size());
     for (auto& h : holes) pl.emit.push_back({off + h.pos, h.kind, h.src});
+    for (auto& h : bholes) pl.b64.push_back({h.src, h.len | B64_TO_ARENA, off + h.pos});
+    for (auto& h : tholes) note(true, h.kind, h.k, off + h.pos, h.len);
     std::pair<uint32_t, uint32_t> r(off, (uint32_t)doc.size());
     doc.clear();
     holes.clear();
+    bholes.clear();
+    tholes.clear();
     return r;
   }
 
@@ -305,8 +324,90 @@ struct PB {
   std::pair<uint32_t, uint32_t> range(uint32_t tok_bytes, uint32_t n, const std::vector<uint32_t>& v,
                                       const std::vector<uint32_t>& bf, const std::vector<uint32_t>& digs,
                                       uint32_t h_type, const std::string& tag);
-  void transfer(const TransferWit& w, size_t idx);
-  void issue(const IssueWit& w, size_t idx);
+  void transfer(const TransferWit& w, size_t idx, const GenTransfer* g = nullptr);
+  void issue(const IssueWit& w, size_t idx, const GenIssue* g = nullptr);
+  // ---- generating calls
+  // Go []byte: null, or base64 of bytes the arena holds (a patch of the shape template)
+  void bytes_json(const GenBytes& b, uint8_t kind, uint32_t k, uint32_t& cached) {
+    if (!b.p) {
+      lit("null");
+      return;
+    }
+    if (cached == NONE) cached = arena_data(b.p, b.len, kind, k);
+    lit("\"");
+    bholes.push_back({(uint32_t)doc.size(), cached, (uint32_t)b.len});
+    doc.append(4 * ((b.len + 2) / 3), '=');
+    lit("\"");
+  }
+  // the outer proof as outer() writes it, but into the arena: the action's Proof hole encodes it
+  std::pair<uint32_t, uint32_t> outer_arena(std::pair<uint32_t, uint32_t> wf, bool has_rc,
+                                            std::pair<uint32_t, uint32_t> rc) {
+    std::string s = "{\"WellFormedness\":\"";
+    uint32_t p_wf = (uint32_t)s.size(), p_rc = 0;
+    s.append(4 * ((wf.second + 2) / 3), '=');
+    s += "\",\"RangeCorrectness\":";
+    if (has_rc) {
+      s += "\"";
+      p_rc = (uint32_t)s.size();
+      s.append(4 * ((rc.second + 2) / 3), '=');
+      s += "\"";
+    } else {
+      s += "null";
+    }
+    s += "}";
+    uint32_t off = arena_put(s.data(), s.size());
+    pl.b64.push_back({wf.first, wf.second | B64_TO_ARENA, off + p_wf});
+    if (has_rc) pl.b64.push_back({rc.first, rc.second | B64_TO_ARENA, off + p_rc});
+    return {off, (uint32_t)s.size()};
+  }
+  void token_list(const GenBytes* owners, uint32_t n, uint32_t tok, std::vector<uint32_t>& own_off) {
+    lit("[");
+    for (uint32_t k = 0; k < n; k++) {
+      lit(k ? ",{\"Owner\":" : "{\"Owner\":");
+      bytes_json(owners[k], SRC_OWNER, k, own_off[k]);
+      lit(",\"Data\":");
+      g1(tok + 64 * k);
+      lit("}");
+    }
+    lit("]");
+  }
+  // token.Metadata of every output (Type, Value, BlindingFactor, Owner, Issuer)
+  void metadata_docs(const std::string& type_js, const GenBytes* owners, uint32_t n, const std::vector<uint32_t>& v,
+                     const std::vector<uint32_t>& bf, std::vector<uint32_t>& own_off, const GenBytes& issuer,
+                     uint32_t& iss_off, std::vector<uint32_t>& ends) {
+    for (uint32_t k = 0; k < n; k++) {
+      lit("{\"Type\":");
+      doc += type_js;
+      lit(",\"Value\":");
+      zr(v[k]);
+      lit(",\"BlindingFactor\":");
+      zr(bf[k]);
+      lit(",\"Owner\":");
+      bytes_json(owners[k], SRC_OWNER, k, own_off[k]);
+      lit(",\"Issuer\":");
+      bytes_json(issuer, SRC_ISSUER, 0, iss_off);
+      lit("}");
+      ends.push_back((uint32_t)doc.size());
+    }
+  }
+  // The documents are written head | rest in one arena block (head: the action up
+  // to the opening quote of Proof; rest: its end and the metadata documents, whose
+  // ends within the block are `ends`).  The order's output block is the head,
+  // base64 of the outer proof, the rest and the commitments' RawBytes.
+  void finish_gen(uint32_t head_len, const std::vector<uint32_t>& ends, std::pair<uint32_t, uint32_t> proof,
+                  uint32_t coms, uint32_t n_out) {
+    std::pair<uint32_t, uint32_t> d = flush_doc();
+    const uint32_t p64 = 4 * ((proof.second + 2) / 3), rest = d.second - head_len;
+    uint32_t o = (uint32_t)pl.out.size();
+    pl.out_off.push_back(o);
+    pl.b64.push_back({d.first, head_len | B64_RAW | B64_L2, o});
+    pl.b64.push_back({proof.first, proof.second | B64_L2, o + head_len});
+    pl.b64.push_back({d.first + head_len, rest | B64_RAW | B64_L2, o + head_len + p64});
+    pl.b64.push_back({coms, (64 * n_out) | B64_RAW | B64_L2, o + head_len + p64 + rest});
+    pl.out.resize(o + head_len + p64 + rest + 64 * n_out, '=');
+    pl.gen_len.push_back(ends[0] + p64);
+    for (size_t k = 1; k < ends.size(); k++) pl.gen_len.push_back(ends[k] - ends[k - 1]);
+  }
   void begin(const uint8_t* seed) { seed_off = arena_data(seed, 32, SRC_SEED); }
   void checks(uint32_t first_pt) {
     TxChecks t;
@@ -521,7 +622,7 @@ std::pair<uint32_t, uint32_t> PB::range(uint32_t tok_bytes, uint32_t n, const st
   return flush_doc();
 }
 
-void PB::transfer(const TransferWit& w, size_t idx) {
+void PB::transfer(const TransferWit& w, size_t idx, const GenTransfer* g) {
   const uint32_t ni = w.n_in, no = w.n_out;
   bool need_range = !(ni == 1 && no == 1);
   std::vector<uint32_t> ov;
@@ -535,7 +636,8 @@ void PB::transfer(const TransferWit& w, size_t idx) {
   // tokens: inputs then outputs, canonical RawBytes (hashed by both transcripts)
   uint32_t tok = arena_alloc(64 * (ni + no));
   for (uint32_t i = 0; i < ni; i++) point(w.inputs + 64 * i, 64, tok + 64 * i, SRC_IN_PT, i);
-  for (uint32_t k = 0; k < no; k++) point(w.outputs + 64 * k, 64, tok + 64 * (ni + k), SRC_OUT_PT, k);
+  if (!g)
+    for (uint32_t k = 0; k < no; k++) point(w.outputs + 64 * k, 64, tok + 64 * (ni + k), SRC_OUT_PT, k);
   std::vector<uint32_t> iv(ni), ibf(ni), ovs(no), obf(no);
   for (uint32_t i = 0; i < ni; i++) {
     iv[i] = zr32(w.in_values + 32 * i, SRC_IN_VAL, i);
@@ -543,9 +645,14 @@ void PB::transfer(const TransferWit& w, size_t idx) {
   }
   for (uint32_t k = 0; k < no; k++) {
     ovs[k] = zr32(w.out_values + 32 * k, SRC_OUT_VAL, k);
-    obf[k] = zr32(w.out_bfs + 32 * k, SRC_OUT_BF, k);
+    // GetTokensWithWitness draws the blinding factors before proving (token/token.go:78-98)
+    obf[k] = g ? rnd("tx/token/bf/" + std::to_string(k)) : zr32(w.out_bfs + 32 * k, SRC_OUT_BF, k);
   }
   uint32_t h_type = hash_pre(arena_data(w.type, w.type_len, SRC_TYPE), (uint32_t)w.type_len);
+  if (g)  // the output commitments H(type) Ped0 + v Ped1 + bf Ped2 into the block both transcripts hash
+    for (uint32_t k = 0; k < no; k++)
+      g1job({{G1B_PED0, h_type}, {G1B_PED1, ovs[k]}, {G1B_PED2, obf[k]}}, NONE, NONE, tok + 64 * (ni + k), NONE,
+            false);
   // range proof first (transfer.go:100-107), then well-formedness
   std::pair<uint32_t, uint32_t> rc(0, 0);
   if (need_range) {
@@ -604,11 +711,40 @@ void PB::transfer(const TransferWit& w, size_t idx) {
   zr(c);
   lit("}");
   std::pair<uint32_t, uint32_t> wfd = flush_doc();
-  outer(wfd, need_range, rc);
+  if (!g) {
+    outer(wfd, need_range, rc);
+    checks(first_pt);
+    return;
+  }
+  // json.Marshal(TransferAction{Inputs, InputCommitments, OutputTokens, Proof, Metadata})
+  std::pair<uint32_t, uint32_t> proof = outer_arena(wfd, need_range, rc);
+  std::vector<uint32_t> own_off(no, NONE), ends;
+  uint32_t iss_off = NONE;
+  lit("{\"Inputs\":[");
+  for (uint32_t i = 0; i < ni; i++) {
+    std::string id = go_json_str(reinterpret_cast<const char*>(g->ids[i].p), g->ids[i].len);
+    lit(i ? ",\"" : "\"");
+    tholes.push_back({(uint32_t)doc.size(), (uint32_t)id.size() - 2, i, SRC_ID});
+    doc.append(id, 1, id.size() - 2);
+    lit("\"");
+  }
+  lit("],\"InputCommitments\":[");
+  for (uint32_t i = 0; i < ni; i++) {
+    if (i) lit(",");
+    g1(tok + 64 * i);
+  }
+  lit("],\"OutputTokens\":");
+  token_list(g->owners, no, tok + 64 * ni, own_off);
+  lit(",\"Proof\":\"");
+  uint32_t head = (uint32_t)doc.size();
+  lit("\",\"Metadata\":{}}");
+  ends.push_back((uint32_t)doc.size());
+  metadata_docs(go_json_str(w.type, w.type_len), g->owners, no, ovs, obf, own_off, GenBytes{nullptr, 0}, iss_off, ends);
+  finish_gen(head, ends, proof, tok + 64 * ni, no);
   checks(first_pt);
 }
 
-void PB::issue(const IssueWit& w, size_t idx) {
+void PB::issue(const IssueWit& w, size_t idx, const GenIssue* g) {
   const uint32_t n = w.n_out;
   std::vector<uint32_t> vv((size_t)n * (pp.exponent > 0 ? (size_t)pp.exponent : 0), 0);
   {
@@ -618,13 +754,17 @@ void PB::issue(const IssueWit& w, size_t idx) {
   begin(w.seed);
   uint32_t first_pt = pl.n_pts;
   uint32_t tok = arena_alloc(64 * n);
-  for (uint32_t k = 0; k < n; k++) point(w.outputs + 64 * k, 64, tok + 64 * k, SRC_OUT_PT, k);
+  if (!g)
+    for (uint32_t k = 0; k < n; k++) point(w.outputs + 64 * k, 64, tok + 64 * k, SRC_OUT_PT, k);
   std::vector<uint32_t> v(n), bf(n);
   for (uint32_t k = 0; k < n; k++) {
     v[k] = zr32(w.values + 32 * k, SRC_OUT_VAL, k);
-    bf[k] = zr32(w.bfs + 32 * k, SRC_OUT_BF, k);
+    bf[k] = g ? rnd("issue/token/bf/" + std::to_string(k)) : zr32(w.bfs + 32 * k, SRC_OUT_BF, k);
   }
   uint32_t h_type = hash_pre(arena_data(w.type, w.type_len, SRC_TYPE), (uint32_t)w.type_len);
+  if (g)
+    for (uint32_t k = 0; k < n; k++)
+      g1job({{G1B_PED0, h_type}, {G1B_PED1, v[k]}, {G1B_PED2, bf[k]}}, NONE, NONE, tok + 64 * k, NONE, false);
   // issue WellFormednessProver (issue/wellformedness.go:74-184)
   const std::string t = "issue/wf";
   uint32_t rt = w.anonymous ? rnd(t + "/r_type") : NONE;
@@ -660,7 +800,25 @@ void PB::issue(const IssueWit& w, size_t idx) {
   lit("}");
   std::pair<uint32_t, uint32_t> wfd = flush_doc();
   std::pair<uint32_t, uint32_t> rc = range(tok, n, v, bf, vv, h_type, "issue/range");
-  outer(wfd, true, rc);
+  if (!g) {
+    outer(wfd, true, rc);
+    checks(first_pt);
+    return;
+  }
+  // json.Marshal(IssueAction{Issuer, OutputTokens `json:"outputs"`, Proof, Anonymous, Metadata})
+  std::pair<uint32_t, uint32_t> proof = outer_arena(wfd, true, rc);
+  std::vector<uint32_t> own_off(n, NONE), ends;
+  uint32_t iss_off = NONE;
+  lit("{\"Issuer\":");
+  bytes_json(g->issuer, SRC_ISSUER, 0, iss_off);
+  lit(",\"outputs\":");
+  token_list(g->owners, n, tok, own_off);
+  lit(",\"Proof\":\"");
+  uint32_t head = (uint32_t)doc.size();
+  lit("\",\"Anonymous\":false,\"Metadata\":null}");
+  ends.push_back((uint32_t)doc.size());
+  metadata_docs(go_json_str(w.type, w.type_len), g->owners, n, v, bf, own_off, g->issuer, iss_off, ends);
+  finish_gen(head, ends, proof, tok, n);
   checks(first_pt);
 }
 
@@ -682,6 +840,10 @@ struct WitView {
   const uint8_t *in_pt, *out_pt, *in_val, *in_bf, *out_val, *out_bf;
   const char* type;
   const uint32_t* digs;  // output k's digit i at k * exponent + i (range_digits)
+  // generating calls: escaped ids (with their quotes), owners, issuer
+  const std::string* ids = nullptr;
+  const GenBytes* owners = nullptr;
+  GenBytes issuer = {nullptr, 0};
 };
 
 static void apply_patches(const PPInfo& pp, const ProofTpl& t, const PieceBase& o, const WitView& w, Plan& pl) {
@@ -694,7 +856,7 @@ static void apply_patches(const PPInfo& pp, const ProofTpl& t, const PieceBase& 
     const uint8_t* src = nullptr;
     uint8_t tmp[32];
     uint32_t d = 0;
-    if (q.kind >= SRC_SIG_R) d = w.digs[q.k];
+    if (q.kind >= SRC_SIG_R && q.kind <= SRC_DIGIT) d = w.digs[q.k];
     switch (q.kind) {
       case SRC_SEED: src = w.seed; break;
       case SRC_IN_PT: src = w.in_pt + 64 * q.k; break;
@@ -711,6 +873,9 @@ static void apply_patches(const PPInfo& pp, const ProofTpl& t, const PieceBase& 
         for (int b = 0; b < 4; b++) tmp[31 - b] = (uint8_t)(d >> (8 * b));
         src = tmp;
         break;
+      case SRC_ID: src = reinterpret_cast<const uint8_t*>(w.ids[q.k].data()) + 1; break;
+      case SRC_OWNER: src = w.owners[q.k].p; break;
+      case SRC_ISSUER: src = w.issuer.p; break;
     }
     if (!q.len) continue;
     if (!q.arena) {
@@ -768,6 +933,76 @@ static WitView view_of(const IssueWit& w, const uint32_t* v) {
   return {w.seed, nullptr, w.outputs, nullptr, nullptr, w.values, w.bfs, w.type, v};
 }
 
+// ---- generating calls: the same machinery over orders.  What an order's plan
+// depends on besides the proof's shape are the lengths of its strings (the
+// documents' layout) and the type (JSON text of the metadata documents); ids,
+// owners and issuer are patched in as bytes.
+static void key_len(std::string& k, const GenBytes& b) {
+  k += b.p ? std::to_string(b.len) : std::string("-");
+  k += ',';
+}
+static std::string key_of(const GenTransfer& o) {
+  std::string k = "g" + std::to_string(o.w.n_in) + "/" + std::to_string(o.w.n_out) + "/" +
+                  std::to_string(o.w.type_len) + "/" + std::string(o.w.type, o.w.type_len) + "/";
+  for (uint32_t i = 0; i < o.w.n_in; i++)
+    k += std::to_string(go_json_str(reinterpret_cast<const char*>(o.ids[i].p), o.ids[i].len).size()) + ",";
+  for (uint32_t j = 0; j < o.w.n_out; j++) key_len(k, o.owners[j]);
+  return k;
+}
+static std::string key_of(const GenIssue& o) {
+  std::string k = "h" + std::to_string(o.w.n_out) + "/" + std::to_string(o.w.type_len) + "/" +
+                  std::string(o.w.type, o.w.type_len) + "/";
+  key_len(k, o.issuer);
+  for (uint32_t j = 0; j < o.w.n_out; j++) key_len(k, o.owners[j]);
+  return k;
+}
+static void plan_one(PB& b, const GenTransfer& x, size_t i) { b.transfer(x.w, i, &x); }
+static void plan_one(PB& b, const GenIssue& x, size_t i) { b.issue(x.w, i, &x); }
+static std::string tpl_digits(const PPInfo& pp, const GenTransfer& o, size_t i, uint32_t* d) {
+  return tpl_digits(pp, o.w, i, d);
+}
+static std::string tpl_digits(const PPInfo& pp, const GenIssue& o, size_t i, uint32_t* d) {
+  return tpl_digits(pp, o.w, i, d);
+}
+static WitView view_of(const GenTransfer& o, const uint32_t* v, std::vector<std::string>& esc) {
+  WitView r = view_of(o.w, v);
+  esc.resize(o.w.n_in);
+  for (uint32_t i = 0; i < o.w.n_in; i++)
+    esc[i] = go_json_str(reinterpret_cast<const char*>(o.ids[i].p), o.ids[i].len);
+  r.ids = esc.data();
+  r.owners = o.owners;
+  return r;
+}
+static WitView view_of(const GenIssue& o, const uint32_t* v, std::vector<std::string>&) {
+  WitView r = view_of(o.w, v);
+  r.owners = o.owners;
+  r.issuer = o.issuer;
+  return r;
+}
+template <class W>
+static WitView view_of(const W& w, const uint32_t* v, std::vector<std::string>&) {
+  return view_of(w, v);
+}
+static uint32_t n_out_of(const TransferWit& w) { return w.n_out; }
+static uint32_t n_out_of(const IssueWit& w) { return w.n_out; }
+static uint32_t n_out_of(const GenTransfer& o) { return o.w.n_out; }
+static uint32_t n_out_of(const GenIssue& o) { return o.w.n_out; }
+// templates per piece: a proof's key is its shape (a handful per batch); an
+// order's key also holds its string lengths, which a batch may vary without
+// bound, so past the cap an order is planned on its own
+template <class W>
+struct TplCap {
+  static constexpr size_t value = (size_t)-1;
+};
+template <>
+struct TplCap<GenTransfer> {
+  static constexpr size_t value = GEN_TPL_CAP;
+};
+template <>
+struct TplCap<GenIssue> {
+  static constexpr size_t value = GEN_TPL_CAP;
+};
+
 template <class W>
 std::string plan_prove_pieces(const PPInfo& pp, size_t n, const W* w, PlanWork& work, WorkPool& pool) {
   size_t np = plan_piece_count(n, pool.size());
@@ -788,10 +1023,29 @@ std::string plan_prove_pieces(const PPInfo& pp, size_t n, const W* w, PlanWork& 
       return;
     }
     TplCache cache;
+    ProofTpl once;  // an order past the cap: planned on its own, its images copied like a template's
     std::vector<uint32_t> vals;
+    std::vector<std::string> esc;
     for (size_t i = lo; i < hi; i++) {
       std::string key = key_of(w[i]);
       ProofTpl* t = cache.find(key);
+      if (!t && cache.v.size() >= TplCap<W>::value) {
+        once.p.clear();
+        once.p.p2_g1out = true;
+        PB b(once.p, pp);
+        plan_one(b, w[i], i);
+        if (!b.err.empty() && work.errs[c].empty()) work.errs[c] = b.err;
+        p.wire.resize((p.wire.size() + 15) & ~(size_t)15, 0);
+        uint32_t ia = (uint32_t)p.wire.size();
+        p.wire.insert(p.wire.end(), once.p.arena.begin(), once.p.arena.end());
+        uint32_t io = (uint32_t)p.wire.size();
+        p.wire.insert(p.wire.end(), once.p.out.begin(), once.p.out.end());
+        PieceBase o = plan_append(p, once.p);
+        p.cp.push_back({ia, (uint32_t)once.p.arena.size(), (uint32_t)o.sec[PS_ARENA], 0});
+        p.cp.push_back({io, (uint32_t)once.p.out.size(), (uint32_t)o.sec[PS_OUT], 1});
+        p.gen_len.insert(p.gen_len.end(), once.p.gen_len.begin(), once.p.gen_len.end());
+        continue;
+      }
       if (!t) {
         cache.v.emplace_back(key, ProofTpl());
         t = &cache.v.back().second;
@@ -808,13 +1062,14 @@ std::string plan_prove_pieces(const PPInfo& pp, size_t n, const W* w, PlanWork& 
         t->img_out = (uint32_t)p.wire.size();
         p.wire.insert(p.wire.end(), t->p.out.begin(), t->p.out.end());
       }
-      vals.assign((size_t)w[i].n_out * (size_t)pp.exponent, 0);
+      vals.assign((size_t)n_out_of(w[i]) * (size_t)pp.exponent, 0);
       std::string de = tpl_digits(pp, w[i], i, vals.data());
       if (!de.empty() && work.errs[c].empty()) work.errs[c] = de;
       PieceBase o = plan_append(p, t->p);
       p.cp.push_back({t->img_arena, (uint32_t)t->p.arena.size(), (uint32_t)o.sec[PS_ARENA], 0});
       p.cp.push_back({t->img_out, (uint32_t)t->p.out.size(), (uint32_t)o.sec[PS_OUT], 1});
-      apply_patches(pp, *t, o, view_of(w[i], vals.data()), p);
+      p.gen_len.insert(p.gen_len.end(), t->p.gen_len.begin(), t->p.gen_len.end());
+      apply_patches(pp, *t, o, view_of(w[i], vals.data(), esc), p);
     }
   });
   for (auto& e : work.errs)
@@ -835,10 +1090,144 @@ std::string plan_prove(const PPInfo& pp, size_t n, const W* w, Plan& out, int th
   std::vector<uint8_t> blob(fp.bytes);
   flat_write(work, fp, blob.data(), std::vector<uint8_t>(C_SIZE, 0).data(), pool);
   plan_unflatten(fp, blob.data(), out);
+  for (size_t k = 0; k < work.used; k++)
+    out.gen_len.insert(out.gen_len.end(), work.pieces[k].gen_len.begin(), work.pieces[k].gen_len.end());
+  return "";
+}
+
+// Go's encoding/json writes U+FFFD for bytes that are no UTF-8 encoding of a
+// scalar value (overlong forms and surrogates included)
+static bool valid_utf8(const uint8_t* s, size_t n) {
+  for (size_t i = 0; i < n;) {
+    uint8_t c = s[i];
+    if (c < 0x80) {
+      i++;
+      continue;
+    }
+    uint32_t len = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : 2, cp = c & (0x7F >> len);
+    if (c < 0xC2 || c > 0xF4 || i + len > n) return false;
+    for (uint32_t k = 1; k < len; k++) {
+      if ((s[i + k] & 0xC0) != 0x80) return false;
+      cp = (cp << 6) | (s[i + k] & 0x3F);
+    }
+    if ((len == 3 && cp < 0x800) || (len == 4 && cp < 0x10000) || cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF))
+      return false;
+    i += len;
+  }
+  return true;
+}
+
+static std::string gen_check_common(const PPInfo& pp, const char* type, size_t type_len, uint32_t n_out,
+                                    const uint8_t* seed, const uint8_t* values, const std::string& at) {
+  if (n_out == 0) return at + ": no outputs";
+  // NewZrFromInt(int64(v)) is negative from 2^63 on [EXT]
+  for (uint32_t k = 0; k < n_out; k++)
+    if (values[32 * k + 24] & 0x80) return at + ": output value " + std::to_string(k) + " is 2^63 or more";
+  if (!seed) return at + ": null seed";
+  if (pp.exponent <= 0) return at + ": public parameters with exponent <= 0";
+  if (!valid_utf8(reinterpret_cast<const uint8_t*>(type), type_len)) return at + ": type is not valid UTF-8";
   return "";
 }
 
 }  // namespace
+
+std::string gen_check(const PPInfo& pp, const GenTransfer& o, size_t idx) {
+  const std::string at = "order " + std::to_string(idx);
+  if (o.w.n_in == 0) return at + ": no inputs";
+  std::string e = gen_check_common(pp, o.w.type, o.w.type_len, o.w.n_out, o.w.seed, o.w.out_values, at);
+  if (!e.empty()) return e;
+  for (uint32_t i = 0; i < o.w.n_in; i++)
+    if (!valid_utf8(o.ids[i].p, o.ids[i].len)) return at + ": input id " + std::to_string(i) + " is not valid UTF-8";
+  return "";
+}
+
+std::string gen_check(const PPInfo& pp, const GenIssue& o, size_t idx) {
+  return gen_check_common(pp, o.w.type, o.w.type_len, o.w.n_out, o.w.seed, o.w.values,
+                          "order " + std::to_string(idx));
+}
+
+struct GenSizeCache {
+  std::vector<std::pair<std::string, std::vector<uint32_t>>> v;
+};
+GenSizeCache* gen_size_cache_new() { return new GenSizeCache(); }
+void gen_size_cache_free(GenSizeCache* c) { delete c; }
+
+// an order's document lengths are those of its key's plan: planned once per key
+template <class W>
+static std::string gen_sizes_t(const PPInfo& pp, const W& o, size_t idx, GenSizeCache* cache, uint32_t* len) {
+  std::string e = gen_check(pp, o, idx);
+  if (!e.empty()) return e;
+  std::string key = key_of(o);
+  const std::vector<uint32_t>* hit = nullptr;
+  for (auto& q : cache->v)
+    if (q.first == key) hit = &q.second;
+  if (!hit) {
+    if (cache->v.size() >= 4 * GEN_TPL_CAP) cache->v.clear();
+    Plan p;
+    PB b(p, pp);
+    plan_one(b, o, idx);
+    cache->v.emplace_back(key, p.gen_len);
+    hit = &cache->v.back().second;
+  }
+  for (size_t k = 0; k < hit->size(); k++) len[k] = (*hit)[k];
+  return "";
+}
+std::string gen_sizes(const PPInfo& pp, const GenTransfer& o, size_t idx, GenSizeCache* c, uint32_t* len) {
+  return gen_sizes_t(pp, o, idx, c, len);
+}
+std::string gen_sizes(const PPInfo& pp, const GenIssue& o, size_t idx, GenSizeCache* c, uint32_t* len) {
+  return gen_sizes_t(pp, o, idx, c, len);
+}
+
+std::string plan_gen_transfers(const PPInfo& pp, size_t n, const GenTransfer* o, Plan& out, int threads) {
+  return plan_prove(pp, n, o, out, threads, 0);
+}
+std::string plan_gen_issues(const PPInfo& pp, size_t n, const GenIssue* o, Plan& out, int threads) {
+  return plan_prove(pp, n, o, out, threads, 0);
+}
+std::string plan_gen_items_transfers(const PPInfo& pp, size_t n, const GenTransfer* o, PlanWork& w, WorkPool& pool) {
+  return plan_prove_pieces(pp, n, o, w, pool);
+}
+std::string plan_gen_items_issues(const PPInfo& pp, size_t n, const GenIssue* o, PlanWork& w, WorkPool& pool) {
+  return plan_prove_pieces(pp, n, o, w, pool);
+}
+
+static size_t der_len_size(size_t n) {
+  size_t k = 1;
+  if (n >= 0x80)
+    for (size_t v = n; v; v >>= 8) k++;
+  return k;
+}
+static uint8_t* der_head(uint8_t* o, uint8_t tag, size_t n) {
+  *o++ = tag;
+  if (n < 0x80) {
+    *o++ = (uint8_t)n;
+    return o;
+  }
+  int k = (int)der_len_size(n) - 1;
+  *o++ = (uint8_t)(0x80 | k);
+  for (int q = k - 1; q >= 0; q--) *o++ = (uint8_t)(n >> (8 * q));
+  return o;
+}
+size_t der_encode_token_request(const GenBytes* const lists[4], const size_t counts[4], uint8_t* out) {
+  size_t body[4], total = 0;
+  for (int f = 0; f < 4; f++) {
+    body[f] = 0;
+    for (size_t i = 0; i < counts[f]; i++) body[f] += 1 + der_len_size(lists[f][i].len) + lists[f][i].len;
+    total += 1 + der_len_size(body[f]) + body[f];
+  }
+  if (!out) return 1 + der_len_size(total) + total;
+  uint8_t* o = der_head(out, 0x30, total);
+  for (int f = 0; f < 4; f++) {
+    o = der_head(o, 0x30, body[f]);
+    for (size_t i = 0; i < counts[f]; i++) {
+      o = der_head(o, 0x04, lists[f][i].len);
+      if (lists[f][i].len) memcpy(o, lists[f][i].p, lists[f][i].len);
+      o += lists[f][i].len;
+    }
+  }
+  return (size_t)(o - out);
+}
 
 std::string plan_prove_transfers(const PPInfo& pp, size_t n, const TransferWit* w, Plan& out, int threads) {
   return plan_prove(pp, n, w, out, threads, [](PB& b, const TransferWit& x, size_t i) { b.transfer(x, i); });

@@ -77,12 +77,20 @@ __global__ void __launch_bounds__(64) k_copy(const CopyJob* jobs, uint32_t n, co
   for (uint32_t b = threadIdx.x; b < j.len; b += blockDim.x) job_copy_byte(j, b, wire, arena, out);
 }
 
-// one workgroup per inner document: threads stride over its 3-byte groups
-__global__ void __launch_bounds__(256) k_b64(const B64Job* jobs, uint32_t n, const uint8_t* arena, uint8_t* out) {
+// one workgroup per inner document: threads stride over its 3-byte groups.
+// level 0 runs the jobs without B64_L2 (inner documents into the outer proof;
+// for the generating calls the outer proof stays in the arena and owners /
+// issuer go into the action and metadata documents there), level 1 those with
+// it (the outer proof into the action's Proof hole, the documents' finished
+// pieces and the commitments into the output); a workgroup of the other level
+// leaves at once.
+__global__ void __launch_bounds__(256) k_b64(const B64Job* jobs, uint32_t n, uint8_t* arena, uint8_t* out,
+                                             uint32_t level) {
   if (blockIdx.x >= n) return;
   B64Job j = jobs[blockIdx.x];
-  uint32_t groups = (j.len + 2) / 3;
-  for (uint32_t g = threadIdx.x; g < groups; g += blockDim.x) b64_group(out + j.dst + 4 * g, arena + j.src, j.len, g);
+  if (((j.len & B64_L2) != 0) != (level != 0)) return;
+  uint32_t units = job_b64_units(j);
+  for (uint32_t u = threadIdx.x; u < units; u += blockDim.x) job_b64_unit(j, u, arena, out);
 }
 
 // context construction

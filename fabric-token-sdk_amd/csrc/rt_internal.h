@@ -196,6 +196,8 @@ struct ScratchLayout {
 struct ftz_batch {
   ftz_ctx* ctx = nullptr;
   bool prover = false;
+  bool gen = false;  // a generating pass (ftz_generate_*): the second k_b64 launch; gen_len is its documents' lengths
+  std::vector<uint32_t> gen_len;
   bool ps = false;  // a Pointcheval-Sanders pass: the unity test and k_verdict_gt in place of the GT bytes and k_verdict
   size_t n = 0;
   PlanWork work;
@@ -229,7 +231,8 @@ int slot_plan_ps(ftz_batch* b, size_t n, const PsIn* items);          // the sam
 int slot_submit(ftz_batch* b, bool upload, bool fetch_codes);      // enqueue (optionally the H2D copy first)
 int slot_wait(ftz_batch* b);                                       // block, collect stats
 void slot_free(ftz_batch* b);                                      // sync + release everything
-int prover_plan(ftz_batch* b, size_t n, const void* wit, int kind);  // kind 0 transfer / 1 issue
+// kind 0 transfer / 1 issue witnesses, 2 transfer / 3 issue orders (GenTransfer / GenIssue)
+int prover_plan(ftz_batch* b, size_t n, const void* wit, int kind);
 int prover_submit(ftz_batch* b, bool upload, bool fetch);
 int prover_wait(ftz_batch* b);
 // results of the last submission that fetched them (valid after slot_wait)

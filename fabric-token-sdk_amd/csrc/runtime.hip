@@ -578,10 +578,19 @@ int prover_plan(ftz_batch* b, size_t n, const void* wit, int kind) {
   int trc = ensure_prover_tables(c);
   if (trc != FTZ_SUCCESS) return trc;
   const PPInfo& pp = c->ptab_ready ? c->pp : c->pp_var;  // the table set's bases only when it exists
-  std::string e = kind == 0
-                      ? plan_prove_items_transfers(pp, n, static_cast<const TransferWit*>(wit), b->work, *c->pool)
-                      : plan_prove_items_issues(pp, n, static_cast<const IssueWit*>(wit), b->work, *c->pool);
+  std::string e;
+  switch (kind) {
+    case 0: e = plan_prove_items_transfers(pp, n, static_cast<const TransferWit*>(wit), b->work, *c->pool); break;
+    case 1: e = plan_prove_items_issues(pp, n, static_cast<const IssueWit*>(wit), b->work, *c->pool); break;
+    case 2: e = plan_gen_items_transfers(pp, n, static_cast<const GenTransfer*>(wit), b->work, *c->pool); break;
+    default: e = plan_gen_items_issues(pp, n, static_cast<const GenIssue*>(wit), b->work, *c->pool); break;
+  }
   if (!e.empty()) return set_err(FTZ_E_INVALID, e);
+  b->gen = kind >= 2;
+  b->gen_len.clear();
+  if (b->gen)
+    for (size_t k = 0; k < b->work.used; k++)
+      b->gen_len.insert(b->gen_len.end(), b->work.pieces[k].gen_len.begin(), b->work.pieces[k].gen_len.end());
   return slot_finish_plan(b, n, true);
 }
 
@@ -1073,7 +1082,9 @@ int prover_submit(ftz_batch* b, bool upload, bool fetch) {
   if (p.n_sp) k_scalar<<<blocks_for(p.n_sp, 256), 256, 0, s>>>(p.sc_post, p.n_sp, p.scal, p.sclist);
   HC(hipEventRecord(e[10], s));
   if (p.n_em) k_emit<<<blocks_for(p.n_em, 256), 256, 0, s>>>(p.emit, p.n_em, p.scal, p.arena);
-  if (p.n_b64) k_b64<<<p.n_b64, 256, 0, s>>>(p.b64, p.n_b64, p.arena, p.out);
+  if (p.n_b64) k_b64<<<p.n_b64, 256, 0, s>>>(p.b64, p.n_b64, p.arena, p.out, 0);
+  // generating calls: the outer proofs (in the arena) into the actions, the documents into the output
+  if (p.n_b64 && b->gen) k_b64<<<p.n_b64, 256, 0, s>>>(p.b64, p.n_b64, p.arena, p.out, 1);
   if (p.n_tx)
     k_verdict<<<blocks_for(p.n_tx, 256), 256, 0, s>>>(p.tx, p.n_tx, p.ck, p.pt_ok, p.hash_ok, p.codes, p.bitmap);
   HC(hipEventRecord(e[13], s));  // total includes the verdict kernel
@@ -1210,12 +1221,68 @@ extern "C" void ftz_prover_destroy(ftz_prover* b) {
   delete b;
 }
 
+// Where the results of a generating call go (ftz_generate_*): the caller's
+// buffers and how far they are filled.  Orders arrive pass by pass, in order.
+struct GenSink {
+  const uint32_t* n_out;  // outputs of every order of the call
+  uint8_t *act, *meta, *coms;
+  size_t *act_off, *meta_off;
+  int32_t* codes;
+  size_t act_w = 0, meta_w = 0, tok = 0;
+};
+
+// A finished generating pass into the sink.  An order's block of the pass
+// output is action | metadata documents | commitments (planner_prove.cpp
+// finish_gen), their lengths in gen_len; an order whose inputs did not decode
+// leaves empty entries and zero commitments.
+static void gen_collect(ftz_ctx* c, ftz_prover* p, size_t lo, GenSink& g) {
+  struct Move {
+    const uint8_t* src;
+    uint8_t* dst;
+    size_t len;
+  };
+  std::vector<Move> mv;
+  mv.reserve(3 * p->n);
+  const uint8_t* out = slot_out(p);
+  size_t q = 0;  // index into gen_len
+  for (size_t i = 0; i < p->n; i++) {
+    const uint32_t no = g.n_out[lo + i];
+    const int32_t code = slot_codes(p)[i];
+    const uint8_t* blk = out + p->fp.out_off[i];
+    const uint32_t* len = p->gen_len.data() + q;
+    q += 1 + no;
+    size_t ml = 0;
+    for (uint32_t k = 0; k < no; k++) ml += len[1 + k];
+    g.codes[lo + i] = code;
+    g.act_off[lo + i] = g.act_w;
+    if (code == E_OK) {
+      mv.push_back({blk, g.act + g.act_w, len[0]});
+      mv.push_back({blk + len[0], g.meta + g.meta_w, ml});
+      if (g.coms) mv.push_back({blk + len[0] + ml, g.coms + 64 * g.tok, (size_t)64 * no});
+      g.act_w += len[0];
+    } else if (g.coms) {
+      memset(g.coms + 64 * g.tok, 0, (size_t)64 * no);
+    }
+    for (uint32_t k = 0; k < no; k++) {
+      g.meta_off[g.tok + k] = g.meta_w;
+      if (code == E_OK) g.meta_w += len[1 + k];
+    }
+    g.tok += no;
+  }
+  // the planning threads copy, as for proofs (prove_chunked)
+  const size_t parts = 16, step = (mv.size() + parts - 1) / parts;
+  c->pool->run(parts, [&](size_t t) {
+    for (size_t k = t * step; k < std::min(mv.size(), (t + 1) * step); k++)
+      if (mv[k].len) memcpy(mv[k].dst, mv[k].src, mv[k].len);
+  });
+}
+
 // One-shot proving of any n: passes of min(opt.batch, 4096) witnesses pipelined through
 // the context's reusable prover slots (plan batch k+1 on the host while batch
 // k runs), proofs concatenated into buf in witness order.
 template <class W>
 static int prove_chunked(ftz_ctx* c, size_t n, const W* w, int kind, uint8_t* buf, size_t cap, size_t* offsets,
-                         int32_t* codes) {
+                         int32_t* codes, GenSink* gs = nullptr) {
   std::lock_guard<std::mutex> lk(c->prove_mu);
   HC(hipSetDevice(c->device));
   using Clk = std::chrono::steady_clock;
@@ -1250,6 +1317,13 @@ static int prove_chunked(ftz_ctx* c, size_t n, const W* w, int kind, uint8_t* bu
     ps.wait_ms += ms(t0, t1);
     if (r != FTZ_SUCCESS) return r;
     size_t lo = k * B, nb = p->fp.cnt[PS_OUT];
+    if (gs) {
+      gen_collect(c, p, lo, *gs);
+      ps.copy_ms += ms(t1, Clk::now());
+      ps.passes++;
+      ps.proofs += p->n;
+      return FTZ_SUCCESS;
+    }
     if (written + nb > cap) return set_err(FTZ_E_INVALID, "proof buffer too small");
     // ~29 MB of proof JSON per 4096-proof pass: copied by the planning threads
     // (one core's memcpy took a third of the host time between passes)
@@ -1334,6 +1408,161 @@ extern "C" int ftz_prove_issues(ftz_ctx* c, size_t n, const ftz_issue_witness* w
   }
   std::vector<IssueWit> t = to_wit(n, w);
   return prove_chunked(c, n, t.data(), 1, buf, cap, offsets, codes);
+}
+
+// ------------------------------------------------------------------ generating calls
+// ftz_generate_*: orders -> GenTransfer / GenIssue (values as 32-byte Zr), the
+// refusals and the documents' sizes from the orders alone, then the prover's
+// passes with the generating plans (prover_plan kind 2 / 3).
+static_assert(sizeof(GenBytes) == sizeof(ftz_bytes) && offsetof(GenBytes, len) == offsetof(ftz_bytes, len),
+              "GenBytes mirrors ftz_bytes");
+static const GenBytes* as_gen(const ftz_bytes* b) { return reinterpret_cast<const GenBytes*>(b); }
+
+struct GenOrders {
+  std::vector<GenTransfer> t;
+  std::vector<GenIssue> is;
+  std::vector<uint8_t> vals;  // every output's value, 32 bytes big-endian
+  std::vector<uint32_t> n_out;
+  size_t tokens = 0;
+};
+static void be32_u64(uint8_t* b, uint64_t v) {
+  memset(b, 0, 32);
+  for (int q = 0; q < 8; q++) b[31 - q] = (uint8_t)(v >> (8 * q));
+}
+static bool bytes_ok(const ftz_bytes* b, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (b[i].len && !b[i].p) return false;
+  return true;
+}
+static std::string to_orders(size_t n, const ftz_transfer_order* o, GenOrders& g) {
+  for (size_t i = 0; i < n; i++) {
+    if ((o[i].n_in && (!o[i].input_ids || !o[i].inputs || !o[i].in_values || !o[i].in_bfs)) ||
+        (o[i].n_out && (!o[i].out_values || !o[i].out_owners)) || (o[i].type_len && !o[i].type) ||
+        (o[i].n_in && !bytes_ok(o[i].input_ids, o[i].n_in)) || (o[i].n_out && !bytes_ok(o[i].out_owners, o[i].n_out)))
+      return "null buffer in order " + std::to_string(i);
+    g.tokens += o[i].n_out;
+  }
+  g.vals.resize(32 * g.tokens + 32);
+  g.t.resize(n);
+  g.n_out.resize(n);
+  size_t t = 0;
+  for (size_t i = 0; i < n; i++) {
+    for (uint32_t k = 0; k < o[i].n_out; k++) be32_u64(&g.vals[32 * (t + k)], o[i].out_values[k]);
+    g.t[i].w = {o[i].inputs, o[i].n_in,  nullptr,   o[i].n_out,    o[i].in_values, o[i].in_bfs, &g.vals[32 * t],
+                nullptr,     o[i].type, o[i].type_len, o[i].seed};
+    g.t[i].ids = as_gen(o[i].input_ids);
+    g.t[i].owners = as_gen(o[i].out_owners);
+    g.n_out[i] = o[i].n_out;
+    t += o[i].n_out;
+  }
+  return "";
+}
+static std::string to_orders(size_t n, const ftz_issue_order* o, GenOrders& g) {
+  for (size_t i = 0; i < n; i++) {
+    if ((o[i].n_out && (!o[i].values || !o[i].owners)) || (o[i].type_len && !o[i].type) ||
+        (o[i].issuer.len && !o[i].issuer.p) || (o[i].n_out && !bytes_ok(o[i].owners, o[i].n_out)))
+      return "null buffer in order " + std::to_string(i);
+    g.tokens += o[i].n_out;
+  }
+  g.vals.resize(32 * g.tokens + 32);
+  g.is.resize(n);
+  g.n_out.resize(n);
+  size_t t = 0;
+  for (size_t i = 0; i < n; i++) {
+    for (uint32_t k = 0; k < o[i].n_out; k++) be32_u64(&g.vals[32 * (t + k)], o[i].values[k]);
+    g.is[i].w = {nullptr, o[i].n_out, &g.vals[32 * t], nullptr, o[i].type, o[i].type_len, 0, o[i].seed};
+    g.is[i].issuer = {o[i].issuer.p, o[i].issuer.len};
+    g.is[i].owners = as_gen(o[i].owners);
+    g.n_out[i] = o[i].n_out;
+    t += o[i].n_out;
+  }
+  return "";
+}
+
+// total action / metadata bytes of the orders; the first refusal fails the call
+template <class G>
+static int gen_total(ftz_ctx* c, size_t n, const G* g, size_t* act, size_t* meta) {
+  GenSizeCache* cache = gen_size_cache_new();
+  std::vector<uint32_t> len;
+  std::string e;
+  *act = *meta = 0;
+  for (size_t i = 0; i < n && e.empty(); i++) {
+    len.assign((size_t)g[i].w.n_out + 1, 0);
+    e = gen_sizes(c->pp, g[i], i, cache, len.data());
+    *act += len[0];
+    for (size_t k = 1; k < len.size(); k++) *meta += len[k];
+  }
+  gen_size_cache_free(cache);
+  return e.empty() ? FTZ_SUCCESS : set_err(FTZ_E_INVALID, e);
+}
+
+template <class O>
+static int generate_size(ftz_ctx* c, size_t n, const O* o, size_t* act, size_t* meta) {
+  if (!c || (n && !o) || !act || !meta) return set_err(FTZ_E_INVALID, "null argument");
+  GenOrders g;
+  std::string e = to_orders(n, o, g);
+  if (!e.empty()) return set_err(FTZ_E_INVALID, e);
+  return g.t.empty() ? gen_total(c, n, g.is.data(), act, meta) : gen_total(c, n, g.t.data(), act, meta);
+}
+
+template <class O>
+static int generate(ftz_ctx* c, size_t n, const O* o, int kind, uint8_t* act, size_t act_cap, size_t* act_off,
+                    uint8_t* meta, size_t meta_cap, size_t* meta_off, uint8_t* coms, int32_t* codes) {
+  if (!c || (n && (!o || !codes)) || !act_off || !meta_off) return set_err(FTZ_E_INVALID, "null argument");
+  act_off[0] = meta_off[0] = 0;
+  if (n == 0) return FTZ_SUCCESS;
+  GenOrders g;
+  std::string e = to_orders(n, o, g);
+  if (!e.empty()) return set_err(FTZ_E_INVALID, e);
+  size_t need_a = 0, need_m = 0;
+  int rc = kind == 2 ? gen_total(c, n, g.t.data(), &need_a, &need_m) : gen_total(c, n, g.is.data(), &need_a, &need_m);
+  if (rc != FTZ_SUCCESS) return rc;
+  if (need_a > act_cap || need_m > meta_cap || (need_a && !act) || (need_m && !meta))
+    return set_err(FTZ_E_INVALID, "generate: buffers too small: need " + std::to_string(need_a) +
+                                      " action bytes and " + std::to_string(need_m) + " metadata bytes");
+  GenSink sink{g.n_out.data(), act, meta, coms, act_off, meta_off, codes};
+  rc = kind == 2 ? prove_chunked(c, n, g.t.data(), 2, nullptr, 0, nullptr, nullptr, &sink)
+                 : prove_chunked(c, n, g.is.data(), 3, nullptr, 0, nullptr, nullptr, &sink);
+  if (rc != FTZ_SUCCESS) return rc;
+  act_off[n] = sink.act_w;
+  meta_off[g.tokens] = sink.meta_w;
+  return FTZ_SUCCESS;
+}
+
+extern "C" int ftz_generate_transfers_size(ftz_ctx* c, size_t n, const ftz_transfer_order* o, size_t* act,
+                                           size_t* meta) {
+  return generate_size(c, n, o, act, meta);
+}
+extern "C" int ftz_generate_issues_size(ftz_ctx* c, size_t n, const ftz_issue_order* o, size_t* act, size_t* meta) {
+  return generate_size(c, n, o, act, meta);
+}
+extern "C" int ftz_generate_transfers(ftz_ctx* c, size_t n, const ftz_transfer_order* o, uint8_t* act, size_t act_cap,
+                                      size_t* act_off, uint8_t* meta, size_t meta_cap, size_t* meta_off,
+                                      uint8_t* coms, int32_t* codes) {
+  return generate(c, n, o, 2, act, act_cap, act_off, meta, meta_cap, meta_off, coms, codes);
+}
+extern "C" int ftz_generate_issues(ftz_ctx* c, size_t n, const ftz_issue_order* o, uint8_t* act, size_t act_cap,
+                                   size_t* act_off, uint8_t* meta, size_t meta_cap, size_t* meta_off, uint8_t* coms,
+                                   int32_t* codes) {
+  return generate(c, n, o, 3, act, act_cap, act_off, meta, meta_cap, meta_off, coms, codes);
+}
+
+extern "C" int ftz_token_request_encode(const ftz_bytes* issues, size_t n_issues, const ftz_bytes* transfers,
+                                        size_t n_transfers, const ftz_bytes* sigs, size_t n_sigs,
+                                        const ftz_bytes* asigs, size_t n_asigs, uint8_t* out, size_t cap,
+                                        size_t* len) {
+  const ftz_bytes* in[4] = {issues, transfers, sigs, asigs};
+  const size_t counts[4] = {n_issues, n_transfers, n_sigs, n_asigs};
+  const GenBytes* lists[4];
+  if (!len) return set_err(FTZ_E_INVALID, "null argument");
+  for (int f = 0; f < 4; f++) {
+    if (counts[f] && (!in[f] || !bytes_ok(in[f], counts[f]))) return set_err(FTZ_E_INVALID, "null buffer in token request");
+    lists[f] = as_gen(in[f]);
+  }
+  *len = der_encode_token_request(lists, counts, nullptr);
+  if (!out || cap < *len) return set_err(FTZ_E_INVALID, "token request buffer too small");
+  der_encode_token_request(lists, counts, out);
+  return FTZ_SUCCESS;
 }
 
 // ------------------------------------------------------------------ token openings

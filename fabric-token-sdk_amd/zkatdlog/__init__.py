@@ -213,6 +213,58 @@ class Context:
         finally:
             p.close()
 
+    def generate_packed(self, kind, ptr, n, tokens):
+        """One-shot ftz_generate_transfers / ftz_generate_issues on a packed order
+        array (_abi.pack_transfer_orders / pack_issue_orders) with `tokens`
+        outputs in all.  Returns numpy arrays (actions uint8, action_off
+        int64[n + 1], metadata uint8, meta_off int64[tokens + 1], commitments
+        uint8[tokens, 64], codes int32[n])."""
+        import numpy as np
+        name = "transfers" if kind == "transfer" else "issues"
+        na, nm = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(getattr(self._lib, "ftz_generate_%s_size" % name)(self._h, n, ptr, ctypes.byref(na), ctypes.byref(nm)),
+               self._lib)
+        act = np.empty(max(1, na.value), dtype=np.uint8)
+        meta = np.empty(max(1, nm.value), dtype=np.uint8)
+        coms = np.zeros((max(1, tokens), 64), dtype=np.uint8)
+        aoff = np.zeros(n + 1, dtype=np.uint64)
+        moff = np.zeros(tokens + 1, dtype=np.uint64)
+        codes = np.zeros(max(1, n), dtype=np.int32)
+        u8p, szp = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_size_t)
+        _check(getattr(self._lib, "ftz_generate_" + name)(
+            self._h, n, ptr, act.ctypes.data_as(u8p), na.value, aoff.ctypes.data_as(szp), meta.ctypes.data_as(u8p),
+            nm.value, moff.ctypes.data_as(szp), coms.ctypes.data_as(u8p),
+            codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), self._lib)
+        return (act[:int(aoff[n])], aoff.astype(np.int64), meta[:int(moff[tokens])], moff.astype(np.int64),
+                coms[:tokens], codes[:n])
+
+    def _generate(self, kind, orders, key):
+        orders = list(orders)
+        arr, keep = (_abi.pack_transfer_orders if kind == "transfer" else _abi.pack_issue_orders)(orders)
+        counts = [len(o[key]) for o in orders]
+        act, aoff, meta, moff, coms, codes = self.generate_packed(kind, arr, len(orders), sum(counts))
+        act, meta = act.tobytes(), meta.tobytes()
+        actions = [act[aoff[i]:aoff[i + 1]] for i in range(len(orders))]
+        metas, cs, t = [], [], 0
+        for c in counts:
+            metas.append([meta[moff[t + k]:moff[t + k + 1]] for k in range(c)])
+            cs.append([coms[t + k].tobytes() for k in range(c)])
+            t += c
+        return actions, metas, cs, [int(c) for c in codes]
+
+    def generate_transfers(self, orders):
+        """Sender.GenerateZKTransfer (crypto/transfer/sender.go:52-88) for each order
+        (dicts as in _abi.pack_transfer_orders): (actions, metadata_lists,
+        commitment_lists, codes) -- json(TransferAction) bytes, per order the
+        json(token.Metadata) of every output and its 64-byte commitment.  A refused
+        order (e.g. a value outside the range) raises DeviceError."""
+        return self._generate("transfer", orders, "out_values")
+
+    def generate_issues(self, orders):
+        """The non-anonymous Issuer.GenerateZKIssue (crypto/issue/nonanonym/
+        nonanonymissuer.go:37-80); as generate_transfers, with json(IssueAction)."""
+        return self._generate("issue", orders, "values")
+
     def commit_tokens(self, openings):
         """token commitments H(type)*Ped0 + v*Ped1 + bf*Ped2 (computeTokens,
         token/token.go:64-76) for (type, value, bf) openings: 64-byte RawBytes each."""
@@ -402,6 +454,22 @@ def decode_token_request(raw):
             items.append(ctypes.string_at(e.p, e.len) if e.len else b"")
         out.append(items)
     return out
+
+
+def encode_token_request(issues, transfers, signatures=(), auditor_signatures=()):
+    """asn1.Marshal(driver.TokenRequest{Issues, Transfers, Signatures,
+    AuditorSignatures}) (host-side, no GPU): the inverse of decode_token_request."""
+    lib = _abi.load()
+    keep, args = [], []
+    for items in (issues, transfers, signatures, auditor_signatures):
+        items = [bytes(x) for x in items]
+        args += [ctypes.cast(_abi.pack_bytes_list(items, keep), ctypes.POINTER(_abi.Bytes)), len(items)]
+    n = ctypes.c_size_t()
+    lib.ftz_token_request_encode(*args, None, 0, ctypes.byref(n))
+    buf = (ctypes.c_uint8 * max(1, n.value))()
+    if lib.ftz_token_request_encode(*args, buf, n.value, ctypes.byref(n)) != 0:
+        raise ValueError(lib.ftz_last_error().decode(errors="replace"))
+    return bytes(buf)[:n.value]
 
 
 def setup_public_params(base, exponent, seed, idemix_pk=b"idemix-issuer-pk", idemix_curve=0):

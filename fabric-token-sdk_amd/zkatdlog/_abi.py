@@ -442,6 +442,76 @@ def pack_issue_witnesses(ws):
     return arr, keep
 
 
+class TransferOrder(ctypes.Structure):
+    _fields_ = [("input_ids", ctypes.c_void_p), ("inputs", ctypes.c_void_p), ("n_in", ctypes.c_uint32),
+                ("in_values", ctypes.c_void_p), ("in_bfs", ctypes.c_void_p),
+                ("out_values", ctypes.c_void_p), ("out_owners", ctypes.c_void_p), ("n_out", ctypes.c_uint32),
+                ("type", ctypes.c_void_p), ("type_len", ctypes.c_size_t), ("seed", ctypes.c_void_p)]
+
+
+class IssueOrder(ctypes.Structure):
+    _fields_ = [("issuer", Bytes), ("values", ctypes.c_void_p), ("owners", ctypes.c_void_p),
+                ("n_out", ctypes.c_uint32), ("type", ctypes.c_void_p), ("type_len", ctypes.c_size_t),
+                ("seed", ctypes.c_void_p)]
+
+
+def pack_bytes_list(items, keep):
+    """ftz_bytes array of byte strings; None -> p = NULL (Go nil), b"" -> a non-NULL p with len 0"""
+    items = list(items)
+    arr = (Bytes * max(1, len(items)))()
+    for i, b in enumerate(items):
+        if b is None:
+            continue
+        c = ctypes.create_string_buffer(bytes(b), max(1, len(b)))
+        keep.append(c)
+        arr[i] = Bytes(ctypes.addressof(c), len(b))
+    keep.append(arr)
+    return ctypes.addressof(arr)
+
+
+def _u64s(vals, keep):
+    arr = (ctypes.c_uint64 * max(1, len(vals)))(*[int(v) for v in vals])
+    keep.append(arr)
+    return ctypes.addressof(arr)
+
+
+def _text(t):
+    return t.encode() if isinstance(t, str) else bytes(t)
+
+
+def pack_transfer_orders(orders):
+    """orders: dicts with ids (str / bytes each), inputs (concatenated 64-byte G1),
+    in_values / in_bfs (ints), out_values (ints < 2^64), owners (bytes or None
+    each), type and seed (32 bytes or None).  Returns (ctypes array, keep-alive list)."""
+    orders = list(orders)
+    keep = []
+    arr = (TransferOrder * max(1, len(orders)))()
+    for i, o in enumerate(orders):
+        t = _text(o["type"])
+        arr[i] = TransferOrder(pack_bytes_list([_text(k) for k in o["ids"]], keep), _buf(o["inputs"], keep),
+                               len(o["ids"]), _buf(_zr32(o["in_values"]), keep), _buf(_zr32(o["in_bfs"]), keep),
+                               _u64s(o["out_values"], keep), pack_bytes_list(o["owners"], keep), len(o["out_values"]),
+                               _buf(t, keep), len(t), _buf(o["seed"], keep))
+    return arr, keep
+
+
+def pack_issue_orders(orders):
+    """orders: dicts with issuer (bytes or None), values, owners, type, seed."""
+    orders = list(orders)
+    keep = []
+    arr = (IssueOrder * max(1, len(orders)))()
+    for i, o in enumerate(orders):
+        t = _text(o["type"])
+        iss = Bytes()
+        if o.get("issuer") is not None:
+            c = ctypes.create_string_buffer(bytes(o["issuer"]), max(1, len(o["issuer"])))
+            keep.append(c)
+            iss = Bytes(ctypes.addressof(c), len(o["issuer"]))
+        arr[i] = IssueOrder(iss, _u64s(o["values"], keep), pack_bytes_list(o["owners"], keep), len(o["values"]),
+                            _buf(t, keep), len(t), _buf(o["seed"], keep))
+    return arr, keep
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("ms", ctypes.c_float * FTZ_NKERNELS), ("jobs", ctypes.c_uint64 * FTZ_NKERNELS)]
 
@@ -462,7 +532,9 @@ SYMBOLS = ["ftz_options_default", "ftz_ctx_create", "ftz_ctx_create_ex", "ftz_ct
            "ftz_ecdsa_create", "ftz_ecdsa_add_identity", "ftz_verify_ecdsa_signatures", "ftz_x509_public_key", "ftz_ecdsa_destroy",
            "ftz_ecdsa_add_signer", "ftz_sign_ecdsa",
            "ftz_prove_transfers", "ftz_prove_issues", "ftz_ctx_prover_stats", "ftz_prover_load_transfers", "ftz_prover_load_issues",
-           "ftz_prover_run", "ftz_prover_submit", "ftz_prover_wait", "ftz_prover_bytes", "ftz_prover_proofs", "ftz_prover_stats", "ftz_prover_destroy"]
+           "ftz_prover_run", "ftz_prover_submit", "ftz_prover_wait", "ftz_prover_bytes", "ftz_prover_proofs", "ftz_prover_stats", "ftz_prover_destroy",
+           "ftz_generate_transfers_size", "ftz_generate_issues_size", "ftz_generate_transfers", "ftz_generate_issues",
+           "ftz_token_request_encode"]
 
 _lib = None
 
@@ -593,6 +665,11 @@ def load():
     lib.ftz_prover_stats.argtypes = [vp, ctypes.POINTER(Stats)]
     lib.ftz_prover_destroy.argtypes = [vp]
     lib.ftz_prover_destroy.restype = None
+    for name, order in (("transfers", TransferOrder), ("issues", IssueOrder)):
+        getattr(lib, "ftz_generate_%s_size" % name).argtypes = [vp, sz, ctypes.POINTER(order), szp, szp]
+        getattr(lib, "ftz_generate_" + name).argtypes = [vp, sz, ctypes.POINTER(order), u8p, sz, szp, u8p, sz, szp,
+                                                         u8p, i32p]
+    lib.ftz_token_request_encode.argtypes = [ctypes.POINTER(Bytes), sz] * 4 + [u8p, sz, szp]
     _lib = lib
     return lib
 

@@ -765,6 +765,82 @@ int ftz_prover_proofs(ftz_prover* p, uint8_t* buf, size_t cap, size_t* offsets, 
 int ftz_prover_stats(const ftz_prover* p, ftz_stats* out);
 void ftz_prover_destroy(ftz_prover* p);
 
+/* ---- actions from cleartext values in one call.
+ * Replaces Sender.GenerateZKTransfer (crypto/transfer/sender.go:52-88) and the
+ * non-anonymous Issuer.GenerateZKIssue (crypto/issue/nonanonym/nonanonymissuer.go:
+ * 37-80): values and owners in, json.Marshal of the action and one
+ * json.Marshal(token.Metadata) per output out.  Everything the reference draws
+ * from crypto/rand comes from the order's 32-byte seed as in ftz_prove_*: output
+ * k's blinding factor is rand("tx/token/bf/<k>") for a transfer and
+ * rand("issue/token/bf/<k>") for an issue, its commitment is H(type) Ped0 +
+ * value Ped1 + bf Ped2, and the proof is the one ftz_prove_* returns for that
+ * witness and seed.  The commitments, the proof, the action and the metadata
+ * documents are all written on the device.
+ *   transfer action: {"Inputs":[ids],"InputCommitments":[canonical RawBytes of the
+ *     decoded inputs],"OutputTokens":[{"Owner","Data"}],"Proof","Metadata":{}}
+ *   issue action: {"Issuer","outputs":[{"Owner","Data"}],"Proof","Anonymous":false,
+ *     "Metadata":null}
+ *   metadata: {"Type","Value","BlindingFactor","Owner","Issuer"}, Issuer null for
+ *     a transfer
+ * Refused with FTZ_E_INVALID and a message naming the order: no inputs, no
+ * outputs, a null seed, a context whose exponent is <= 0, a type or id that is
+ * not valid UTF-8 (Go would write U+FFFD and the action would not round-trip), an
+ * output value >= 2^63 ([EXT]: NewZrFromInt(int64(v)) is negative there), and --
+ * except for the 1-in/1-out transfer, which has no range proof -- a value >=
+ * base^exponent, as ftz_prove_* refuses it.  The sum of inputs and outputs is not
+ * checked, as in the reference; the verifier rejects an unbalanced action. */
+typedef struct {
+  const ftz_bytes* input_ids;  /* n_in ledger keys (TransferAction.Inputs), UTF-8           */
+  const uint8_t* inputs;       /* n_in x 64-byte G1 (the ledger tokens' Data), gnark rules  */
+  uint32_t n_in;
+  const uint8_t* in_values;    /* n_in x 32-byte BE Zr (the inputs' token.Metadata)         */
+  const uint8_t* in_bfs;       /* n_in x 32-byte BE Zr                                      */
+  const uint64_t* out_values;  /* n_out (GenerateZKTransfer takes []uint64)                 */
+  const ftz_bytes* out_owners; /* n_out; p == NULL: Go nil (JSON null), p != NULL && len == 0: "" */
+  uint32_t n_out;
+  const char* type;
+  size_t type_len;
+  const uint8_t* seed;         /* 32 bytes, as ftz_transfer_witness.seed                    */
+} ftz_transfer_order;
+typedef struct {
+  ftz_bytes issuer;            /* Signer.Serialize(); NULL / empty as for owners            */
+  const uint64_t* values;      /* n_out                                                     */
+  const ftz_bytes* owners;     /* n_out                                                     */
+  uint32_t n_out;
+  const char* type;
+  size_t type_len;
+  const uint8_t* seed;         /* 32 bytes                                                  */
+} ftz_issue_order;
+/* Exact byte counts of the two buffers below, from the orders alone (every
+ * document has a fixed length given the lengths of its strings). */
+int ftz_generate_transfers_size(ftz_ctx* ctx, size_t n, const ftz_transfer_order* o, size_t* action_bytes,
+                                size_t* meta_bytes);
+int ftz_generate_issues_size(ftz_ctx* ctx, size_t n, const ftz_issue_order* o, size_t* action_bytes,
+                             size_t* meta_bytes);
+/* One call: action i at actions[action_off[i] .. action_off[i+1]), the metadata of
+ * output t (counted over all orders, T in total) at meta[meta_off[t] ..
+ * meta_off[t+1]), its commitment (canonical RawBytes) at commitments + 64 t
+ * (commitments may be NULL).  codes[i] = FTZ_ERR_PARSE when an input commitment of
+ * order i does not decode: its action and metadata entries are then empty and
+ * its commitment slots zero; other orders are unaffected.  A capacity that is too
+ * small: FTZ_E_INVALID with the needed sizes in ftz_last_error (ask
+ * ftz_generate_*_size first).  Runs through the slots, streams and host statistics
+ * of ftz_prove_*; thread-safety is the same. */
+int ftz_generate_transfers(ftz_ctx* ctx, size_t n, const ftz_transfer_order* o, uint8_t* actions, size_t action_cap,
+                           size_t* action_off, uint8_t* meta, size_t meta_cap, size_t* meta_off,
+                           uint8_t* commitments, int32_t* codes);
+int ftz_generate_issues(ftz_ctx* ctx, size_t n, const ftz_issue_order* o, uint8_t* actions, size_t action_cap,
+                        size_t* action_off, uint8_t* meta, size_t meta_cap, size_t* meta_off, uint8_t* commitments,
+                        int32_t* codes);
+/* The inverse of ftz_token_request_decode: minimal DER, exactly
+ * asn1.Marshal(driver.TokenRequest{Issues, Transfers, Signatures,
+ * AuditorSignatures}).  With the last two empty, followed by the txID, it is the
+ * message ftz_verify_signed_token_requests rebuilds.  *len receives the length;
+ * cap < *len (or out == NULL): FTZ_E_INVALID after writing *len. */
+int ftz_token_request_encode(const ftz_bytes* issues, size_t n_issues, const ftz_bytes* transfers, size_t n_transfers,
+                             const ftz_bytes* signatures, size_t n_signatures, const ftz_bytes* auditor_signatures,
+                             size_t n_auditor_signatures, uint8_t* out, size_t cap, size_t* len);
+
 #ifdef __cplusplus
 }
 #endif
