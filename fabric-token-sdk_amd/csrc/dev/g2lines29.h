@@ -1,20 +1,25 @@
 // The pair-2 line chain of k_g2lines1 (one lane per membership digit) on the
 // carry-free balanced form: the 88 Miller lines of t' evaluated at R (65
 // doublings, 21 NAF additions, 2 Frobenius lines) with q2 values and the
-// product-scanned Fp2 products of dev/g2x29.h, written in EvLineDev's balanced
-// planes as the 32-bit chain (job_g2lines_parts) writes them.
+// scanned sums of Fp2 products of dev/g2x29.h (q2_scan), written in EvLineDev's
+// balanced planes as the 32-bit chain (job_g2lines_parts) writes them.
 //
 // Same points as the 32-bit chain, and the same lines up to one factor in Fp
-// per line: the doubling runs on 4 T (homogeneous projective, the same point)
-// so that no halving is needed -- A' = XY, G' = B + F: 4 X3 = 2 A'(B - F),
-// 4 Y3 = G'^2 - 12 E^2, 4 Z3 = 4 B H -- and every later line is homogeneous in
-// T's coordinates.  A line scaled by an element of Fp multiplies the Miller
-// value by an element the final exponentiation sends to 1, so every GT byte is
-// identical (tests/test_sextet.py test_g2_lines_carry_free checks them).
+// per line.  T is homogeneous projective, so any common factor of (X : Y : Z)
+// is free, and every later line is homogeneous in T's coordinates: the
+// doubling runs on 4 T so that no halving is needed, the addition on -T.  A
+// line scaled by an element of Fp multiplies the Miller value by an element
+// the final exponentiation sends to 1, so every GT byte is identical
+// (tests/test_sextet.py test_g2_lines_carry_free checks them).  The multiples
+// of xP and yP the lines take are formed once per job (G2LP).
 //
-// Bounds: every value between operations is balanced (q2_mulb / q2_sqrb /
-// f29_lin2 / f29_lin4 outputs: limbs in [-2^28, 2^28], |value| <= p/2 + e);
-// q2_mulb's operands are balanced or differences of two balanced values.
+// Bounds: T's coordinates between steps have balanced limbs and |value| <=
+// 0.7 p, and every line coefficient is balanced with |value| <= 0.52 p; sums
+// and small multiples of such values are formed limb by limb without a sweep
+// where they are only multiplied.  Each step documents the (B, L) of its
+// intermediates against q2_scan's contract; both steps map the bound of T to
+// itself (their outputs are at most 0.55 p), so it holds along the 88-step
+// chain and any longer one (tests/native/g2fused_main.cpp feeds 1,000 steps).
 #pragma once
 #include "g2x29.h"
 
@@ -46,71 +51,78 @@ FTS_HD f29 g2c_f(int i) {
 FTS_HD q2 g2c_q(int i) { return {g2c_f(i), g2c_f(i + 1)}; }
 FTS_HD q2 q2_one29() { return {g2c_f(G2C_ONE), q2_zero().c1}; }
 
-FTS_HD q2 q2_scaleb(const q2& a, int32_t c) { return q2_lin2b(a, c, a, 0); }
-
-// a (Fp2) times s (Fp), both balanced: two rows scanned together
-FTS_HD q2 q2_mulfb(const q2& a, const f29& s) {
-  FTS_COUNT_MAD(128);
-  FTS_SCHED_FENCE();
-  Scan2 st;
-  st.ar = st.ai = 0;
-  q2 r;
-#pragma unroll
-  for (int k = 0; k < 17; k++) {
-    int64_t re = 0, im = 0;
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      const int j = k - i;
-      if (j < 0 || j > 8) continue;
-      re += (int64_t)a.c0.l[i] * s.l[j];
-      im += (int64_t)a.c1.l[i] * s.l[j];
-    }
-    scan2_step(st, k, re, im, r);
-  }
-  r.c0.l[8] = (int32_t)st.ar;
-  r.c1.l[8] = (int32_t)st.ai;
-  return r;
+// The multiples of P's coordinates the evaluated lines take, formed once per
+// job: -yP and -xP (balanced, negated limb by limb) and 3 xP (unnormalised:
+// L = 3, B = 1.56, a multiplicand only)
+struct G2LP {
+  f29 nyP, nxP, xP3;
+};
+FTS_HD G2LP g2l_pmults(const f29& yP, const f29& xP) {
+  return {f29_neg(yP), f29_neg(xP), f29_add(xP, f29_add(xP, xP))};
 }
 
 // Each step hands its three evaluated coefficients to emit(c, value) (c = 0:
 // c0, 1: c3, 2: c4) as soon as they are formed, so that none of them stays live
-// through the rest of the step.
+// through the rest of the step.  Every coefficient leaves a reduction with no
+// linear term, so it is balanced with B <= 0.52 as the Miller kernels expect.
+//
+// Both steps take and return T = (X, Y, Z) with balanced limbs (L = 1) and
+//   |X|, |Y|, |Z| <= 0.7 p
+// (B, L of every intermediate in comments; "column" is the budget of dev/g2x29.h
+// q2_scan, at most 118) and return them <= 0.55 p.  The chain starts from
+// (Qx, Qy, 1), all <= 0.52 p.
 //
 // T <- 4 (2T) = 2T; the line (-H, 3J, I) evaluated: c0 = -H yP, c3 = 3 X^2 xP,
-// c4 = E - B
+// c4 = K = E - B.  With B = Y^2, H = 2 Y Z = Y (2Z), E = 3 b' Z^2 (E = K + B):
+//   4 X3 = 2 X Y (B - 3E) = (X 2Y)(-2E - K),
+//   4 Y3 = (B + 3E)^2 - 12 E^2 = 4 B^2 - 3 K^2 = (2B)(2B) - K (3K),
+//   4 Z3 = 4 B H = (2B)(2H):
+// the factors 2 and 4 are limb-wise multiples of a multiplicand, B - 3E and
+// 4 Y3 take no reduction of their own terms, and K is the one carry sweep left
+// (it leaves as a line coefficient, E and B feed the products).
+// 3S + 7M + 2 Fp2 x Fp in eleven reductions and one sweep.
 template <class Emit>
-FTS_HD void g2l_dbl(q2& X, q2& Y, q2& Z, const f29& yP, const f29& xP, const Emit& emit) {
-  const q2 B = q2_sqrb(Y);
-  const q2 C = q2_sqrb(Z);
-  const q2 H = q2_lin3b(q2_sqrb(q2_lin2b(Y, 1, Z, 1)), 1, B, -1, C, -1);  // 2 Y Z
-  emit(0, q2_mulfb(q2_neg(H), yP));
-  emit(1, q2_scaleb(q2_mulfb(q2_sqrb(X), xP), 3));
-  const q2 E = q2_mulb(C, g2c_q(G2C_B3));  // 3 b' Z^2
-  emit(2, q2_lin2b(E, 1, B, -1));
-  X = q2_scaleb(q2_mulb(q2_mulb(X, Y), q2_lin2b(B, 1, E, -3)), 2);
-  Y = q2_lin2b(q2_sqrb(q2_lin2b(B, 1, E, 3)), 1, q2_sqrb(E), -12);
-  Z = q2_scaleb(q2_mulb(B, H), 4);
+FTS_HD void g2l_dbl(q2& X, q2& Y, q2& Z, const G2LP& P, const Emit& emit) {
+  const q2 B = q2_sqrb(Y);                                 // 2 x 0.49 / 169 + 0.5: (0.51, 1), column 32
+  const q2 H = q2_mulb(Y, q2_add(Z, Z));                   // (0.51, 1), column 32
+  emit(0, q2s_mulf(H, P.nyP));                             // (0.51, 1), column 8
+  emit(1, q2s_mulf(q2_sqrb(X), P.xP3));                    // X^2: (0.51, 1); 0.51 x 1.56 / 169 + 0.5: (0.51, 1), column 24
+  const q2 E = q2_mulb(q2_sqrb(Z), g2c_q(G2C_B3));         // Z^2, E: (0.51, 1)
+  const q2 K = q2_lin2b(E, 1, B, -1);                      // (0.5001, 1)
+  emit(2, K);
+  const q2 M2 = q2_mulb(X, q2_add(Y, Y));                  // (0.51, 1), column 32
+  const q2 Wn = q2_neg(q2_add(q2_add(E, E), K));           // -2E - K = B - 3E: (1.53, 3), a multiplicand only
+  const q2 B2 = q2_add(B, B);                              // (1.02, 2)
+  const q2 K3n = q2_neg(q2_add(K, q2_add(K, K)));          // (1.51, 3)
+  X = q2_mulb(M2, Wn);                                     // 2 x 0.51 x 1.53 / 169 + 0.5: (0.51, 1), column 48
+  Y = q2s_mul2(B2, B2, K, K3n);                            // 2 (1.05 + 0.76) / 169 + 0.5: (0.53, 1), column 64 + 48
+  Z = q2_mulb(B2, q2_add(H, H));                           // 2 x 1.02 x 1.02 / 169 + 0.5: (0.52, 1), column 64
 }
 
-// T <- T + (Qx, Qy) (affine, balanced); the line (L, -O, Qx O - L Qy)
-// evaluated: c0 = L yP, c3 = -O xP, c4 = Qx O - L Qy.  (The two sums of two
-// products with one reduction each did not pay: profiles/r05/g2_fused_sums_ab.txt.)
+// T <- T + (Qx, Qy) ((Qx, Qy) affine, balanced, B <= 0.52), the projective
+// triple of the 32-bit chain times -1; the line (L, -O, Qx O - L Qy) evaluated:
+// c0 = L yP, c3 = -O xP, c4 = Qx O - L Qy.  With L' = -L = Qx Z - X,
+// O = Y - Qy Z, D = L'^2, E' = L' D, G = X D, H = -E' - 2G + Z O^2:
+//   X3 = L' H,  Y3 = (H - G) O - Y E',  Z3 = E' Z.
+// 2S + 11M + 2 Fp2 x Fp in thirteen reductions, no sweep: O, L' and H take
+// their linear terms in the reduction, c4 and Y3 are sums of two products.
 template <class Emit>
-FTS_HD void g2l_add(q2& X, q2& Y, q2& Z, const q2& Qx, const q2& Qy, const f29& yP, const f29& xP,
-                    const Emit& emit) {
-  const q2 O = q2_lin2b(Y, 1, q2_mulb(Qy, Z), -1);
-  const q2 L = q2_lin2b(X, 1, q2_mulb(Qx, Z), -1);
-  emit(0, q2_mulfb(L, yP));
-  emit(1, q2_mulfb(q2_neg(O), xP));
-  emit(2, q2_lin2b(q2_mulb(Qx, O), 1, q2_mulb(L, Qy), -1));
-  const q2 D = q2_sqrb(L);
-  const q2 E = q2_mulb(L, D);
-  const q2 G = q2_mulb(X, D);
-  const q2 H = q2_lin3b(E, 1, G, -2, q2_mulb(Z, q2_sqrb(O)), 1);
-  const q2 Y3 = q2_lin2b(q2_mulb(q2_subr(G, H), O), 1, q2_mulb(Y, E), -1);
-  X = q2_mulb(L, H);
+FTS_HD void g2l_add(q2& X, q2& Y, q2& Z, const q2& Qx, const q2& Qy, const G2LP& P, const Emit& emit) {
+  const q2 O = q2s_mul_add(q2_neg(Qy), Z, Y);              // 0.01 + 0.5 + 0.7: (1.21, 1), column 16
+  const q2 Lp = q2s_mul_add(Qx, Z, q2_neg(X));             // (1.21, 1)
+  emit(0, q2s_mulf(Lp, P.nyP));                            // 0.63 / 169 + 0.5: (0.51, 1), column 8
+  emit(1, q2s_mulf(O, P.nxP));                             // (0.51, 1)
+  emit(2, q2s_mul2(Qx, O, Lp, Qy));                        // 2 (0.63 + 0.63) / 169 + 0.5001: (0.516, 1), column 32
+  const q2 D = q2_sqrb(Lp);                                // 2 x 1.47 / 169 + 0.5: (0.52, 1), column 32
+  const q2 Ep = q2_mulb(Lp, D);                            // (0.51, 1)
+  const q2 G = q2_mulb(X, D);                              // (0.51, 1)
+  const q2 nE = q2_neg(Ep);
+  // Z O^2 / R - E' - 2G: O^2 is (0.52, 1); H: 0.01 + 0.5 + 0.51 + 1.02: (2.04, 1)
+  const q2 H = q2s_mul_add(Z, q2_sqrb(O), q2_subr(nE, q2_add(G, G)));
+  X = q2_mulb(Lp, H);                                      // 2 x 1.21 x 2.04 / 169 + 0.5: (0.53, 1), column 16
+  const q2 Y3 = q2s_mul2(q2_subr(H, G), O, Y, nE);         // 2 (2.55 x 1.21 + 0.7 x 0.51) / 169 + 0.5: (0.55, 1), column 32 + 16
+  Z = q2_mulb(Ep, Z);                                      // (0.51, 1)
   Y = Y3;
-  Z = q2_mulb(E, Z);
 }
 
 FTS_HD void evline_put_b(EvLineDev* base, uint32_t s, int c, uint32_t idx, uint32_t njobs, const f29& b) {
@@ -164,7 +176,7 @@ FTS_HD void g2lines_chain_x29(const g2a& Q, const G2Job& g, const PairJob& j, G2
   g2out[g.out] = d;
   const g1a P = g1_load(pts[j.p2]);
   const bool use = !(P.inf || Q.inf);
-  const f29 yP = f29_breduce(f29_from_fp(P.y)), xP = f29_breduce(f29_from_fp(P.x));
+  const G2LP pm = g2l_pmults(f29_breduce(f29_from_fp(P.y)), f29_breduce(f29_from_fp(P.x)));
   const q2 Qx = q2_from_fp2(Q.x), Qy = q2_from_fp2(Q.y);
   q2 X = Qx, Y = Qy, Z = q2_one29();
 #pragma nounroll
@@ -177,7 +189,7 @@ FTS_HD void g2lines_chain_x29(const g2a& Q, const G2Job& g, const PairJob& j, G2
       evline_put_b(lines, (uint32_t)s, 2 * c + 1, idx, njobs, w.c1);
     };
     if (t == STEP_DBL) {
-      g2l_dbl(X, Y, Z, yP, xP, emit);
+      g2l_dbl(X, Y, Z, pm, emit);
     } else {
       q2 Ax = Qx, Ay = Qy;
       if (t == STEP_FROB1 || t == STEP_FROB2) {
@@ -190,7 +202,7 @@ FTS_HD void g2lines_chain_x29(const g2a& Q, const G2Job& g, const PairJob& j, G2
       } else if (t == STEP_SUB) {
         Ay = q2_neg(Qy);
       }
-      g2l_add(X, Y, Z, Ax, Ay, yP, xP, emit);
+      g2l_add(X, Y, Z, Ax, Ay, pm, emit);
     }
   }
 }

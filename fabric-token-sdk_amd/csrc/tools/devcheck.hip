@@ -322,3 +322,155 @@ extern "C" int ftz_devcheck_g1_jobs(int device, uint32_t n, const uint32_t* jobs
   delete[] hj;
   return ok ? -(int)e : -1000;
 }
+
+// ---- the G2 table (DC_G2_OPS), as ftz_devcheck_g1_info / ftz_devcheck_g1 are for DC_G1_OPS
+template <int OP, uint32_t NIN, uint32_t NOUT>
+__global__ void __launch_bounds__(256) k_devcheck_g2(uint32_t n, const uint32_t* in, uint32_t* out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  dc_g2_apply<OP>(in + (size_t)j * NIN, out + (size_t)j * NOUT);
+}
+extern "C" int ftz_devcheck_g2_info(int op, char name[32], uint32_t* nin, uint32_t* nout) {
+  if (op >= 0 && op < DC_G2_OP_COUNT) {
+    const DcInfo& e = dc_g2_table()[op];
+    strncpy(name, e.name, 31);
+    name[31] = 0;
+    *nin = e.nin;
+    *nout = e.nout;
+  }
+  return DC_G2_OP_COUNT;
+}
+extern "C" int ftz_devcheck_g2(int device, int op, uint32_t n, uint32_t block, const uint32_t* in, uint32_t* out) {
+  if (op < 0 || op >= DC_G2_OP_COUNT || n == 0 || (block != 64 && block != 256) || !in || !out) return -1000;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return -(int)e;
+  const DcInfo& info = dc_g2_table()[op];
+  const uint32_t blocks = (n + block - 1) / block;
+  const size_t in_bytes = (size_t)n * info.nin * 4, out_bytes = (size_t)blocks * block * info.nout * 4;
+  uint32_t *din = nullptr, *dout = nullptr;
+  if ((e = hipMalloc(&din, in_bytes)) == hipSuccess && (e = hipMalloc(&dout, out_bytes)) == hipSuccess &&
+      (e = hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemset(dout, DC_SENTINEL & 0xFF, out_bytes)) == hipSuccess) {
+    switch (op) {
+#define DC_X(name, nin, nout)                                              \
+  case DC_##name:                                                          \
+    k_devcheck_g2<DC_##name, nin, nout><<<blocks, block>>>(n, din, dout); \
+    break;
+      DC_G2_OPS(DC_X)
+#undef DC_X
+    }
+    if ((e = hipGetLastError()) == hipSuccess && (e = hipDeviceSynchronize()) == hipSuccess)
+      e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  return -(int)e;
+}
+
+// ---- the G2 stage as the verifier runs it (tests/test_gpu_g2_fused.py): k_tab_g2
+// for the window table of the four bases, then k_g2_part, k_g2_sum, k_g2_binv
+// and k_g2lines1 themselves (k_g2.hip compiled into this tool) with the
+// runtime's launch shapes, over n membership jobs the caller describes.
+//   jobs:  n x 5 words: nfix (1..3), the scalar index of each of the three
+//          fixed terms (term f is base f; unused ones ignored), the pts index of R
+//   bases: 4 x 32 words (G2Dev);  scal: n_scal x 8 words (< r);  pts: n_pts x 16
+//          words (G1Dev, all-zero: infinity)
+// Every index is checked before anything runs (-1000).
+//   g2out: n x 64 words, the device's t' (G2Dev, all-zero: infinity) then the
+//          host's from the 32-bit code (job_g2_part, job_g2lines_parts)
+//   lines_dev, lines_host: 88 x 6 x n x 10 words each (EvLineDev planes,
+//          evl_off): the device's evaluated lines and the 32-bit host chain's
+#include "../k_g2.hip"
+
+extern "C" int ftz_devcheck_g2_jobs(int device, uint32_t n, const uint32_t* jobs, const uint32_t* bases, uint32_t n_scal,
+                                    const uint32_t* scal, uint32_t n_pts, const uint32_t* pts, uint32_t* g2out,
+                                    int32_t* lines_dev, int32_t* lines_host) {
+  if (n == 0 || n > 4096 || n_scal == 0 || n_scal > 65536 || n_pts == 0 || n_pts > 65536 || !jobs || !bases || !scal ||
+      !pts || !g2out || !lines_dev || !lines_host)
+    return -1000;
+  G2Job* hj = new G2Job[n];
+  PairJob* hp = new PairJob[n];
+  bool ok = true;
+  for (uint32_t j = 0; j < n; j++) {
+    const uint32_t* q = jobs + (size_t)j * 5;
+    G2Job g{};
+    ok = ok && q[0] >= 1 && q[0] <= 3 && q[4] < n_pts;
+    g.nfix = (uint8_t)q[0];
+    for (int f = 0; f < 3; f++) {
+      g.fbase[f] = (uint8_t)f;
+      g.fscal[f] = f < (int)q[0] ? q[1 + f] : 0;
+      ok = ok && g.fscal[f] < n_scal;
+    }
+    g.out = j;
+    hj[j] = g;
+    hp[j] = PairJob{0, q[4], j, 0, NONE};
+  }
+  const uint32_t t2 = G2B_COUNT * G2TAB_WINDOWS * G2TAB_DIGITS;
+  const size_t line_words = (size_t)MILLER_LINES * 6 * n * EVL_REC;
+  hipError_t e = hipSuccess;
+  if (ok) e = hipSetDevice(device);
+  G2Job* dj = nullptr;
+  PairJob* dp = nullptr;
+  uint32_t *dscal = nullptr, *dpts = nullptr;
+  G2Dev *dbases = nullptr, *dtab = nullptr, *dout = nullptr;
+  G2PartDev* dpart = nullptr;
+  EvLineDev* dlines = nullptr;
+  G2Dev* htab = new G2Dev[t2];
+  G2Dev* res = new G2Dev[n];
+  if (ok && e == hipSuccess && (e = hipMalloc(&dj, sizeof(G2Job) * n)) == hipSuccess &&
+      (e = hipMalloc(&dp, sizeof(PairJob) * n)) == hipSuccess && (e = hipMalloc(&dscal, 32 * (size_t)n_scal)) == hipSuccess &&
+      (e = hipMalloc(&dpts, 64 * (size_t)n_pts)) == hipSuccess && (e = hipMalloc(&dbases, sizeof(G2Dev) * G2B_COUNT)) == hipSuccess &&
+      (e = hipMalloc(&dtab, sizeof(G2Dev) * (size_t)t2)) == hipSuccess && (e = hipMalloc(&dout, sizeof(G2Dev) * n)) == hipSuccess &&
+      (e = hipMalloc(&dpart, sizeof(G2PartDev) * 4 * (size_t)n)) == hipSuccess &&
+      (e = hipMalloc(&dlines, line_words * 4)) == hipSuccess &&
+      (e = hipMemcpy(dj, hj, sizeof(G2Job) * n, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dp, hp, sizeof(PairJob) * n, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dscal, scal, 32 * (size_t)n_scal, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dpts, pts, 64 * (size_t)n_pts, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemcpy(dbases, bases, sizeof(G2Dev) * G2B_COUNT, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemset(dout, 0xA5, sizeof(G2Dev) * n)) == hipSuccess &&
+      (e = hipMemset(dlines, 0xA5, line_words * 4)) == hipSuccess) {
+    const uint32_t(*sc)[8] = reinterpret_cast<const uint32_t(*)[8]>(dscal);
+    k_tab_g2<<<(t2 + 63) / 64, 64>>>(dbases, t2, dtab);
+    k_g2_part<<<(4 * n + 63) / 64, 64>>>(dj, n, sc, dtab, dpart);
+    k_g2_sum<<<(n + 63) / 64, 64>>>(n, dpart);
+    k_g2_binv<<<(n + 255) / 256, 256>>>(n, dpart);
+    k_g2lines1<<<(n + 63) / 64, 64>>>(dj, dp, n, dpart, dout, reinterpret_cast<const G1Dev*>(dpts), dlines);
+    if ((e = hipGetLastError()) == hipSuccess && (e = hipDeviceSynchronize()) == hipSuccess &&
+        (e = hipMemcpy(res, dout, sizeof(G2Dev) * n, hipMemcpyDeviceToHost)) == hipSuccess &&
+        (e = hipMemcpy(lines_dev, dlines, line_words * 4, hipMemcpyDeviceToHost)) == hipSuccess)
+      e = hipMemcpy(htab, dtab, sizeof(G2Dev) * (size_t)t2, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dj);
+  (void)hipFree(dp);
+  (void)hipFree(dscal);
+  (void)hipFree(dpts);
+  (void)hipFree(dbases);
+  (void)hipFree(dtab);
+  (void)hipFree(dout);
+  (void)hipFree(dpart);
+  (void)hipFree(dlines);
+  if (ok && e == hipSuccess) {
+    // the host's 32-bit code on the device's table (its entries are the
+    // runtime's own k_tab_g2 points; t' does not depend on their form)
+    const uint32_t(*sc)[8] = reinterpret_cast<const uint32_t(*)[8]>(scal);
+    G2PartDev* part = new G2PartDev[4 * (size_t)n];
+    G2Dev* host = new G2Dev[n];
+    for (uint32_t j = 0; j < n; j++)
+      for (int q = 0; q < 4; q++) job_g2_part(hj[j], q, sc, htab, part[(size_t)q * n + j]);
+    for (uint32_t j = 0; j < n; j++)
+      job_g2lines_parts(hj[j], hp[j], part, host, reinterpret_cast<const G1Dev*>(pts),
+                        reinterpret_cast<EvLineDev*>(lines_host), j, n);
+    for (uint32_t j = 0; j < n; j++) {
+      memcpy(g2out + (size_t)j * 64, &res[j], 128);
+      memcpy(g2out + (size_t)j * 64 + 32, &host[j], 128);
+    }
+    delete[] host;
+    delete[] part;
+  }
+  delete[] res;
+  delete[] htab;
+  delete[] hp;
+  delete[] hj;
+  return ok ? -(int)e : -1000;
+}

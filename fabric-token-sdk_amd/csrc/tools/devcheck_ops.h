@@ -13,6 +13,7 @@
 #pragma once
 #include "../dev/fp_wide.h"
 #include "../dev/fp29.h"
+#include "../dev/g2lines29.h"
 #include "../dev/p256.h"
 #include "../dev/sha256.h"
 
@@ -302,6 +303,85 @@ FTS_HD void dc_g1_apply(const uint32_t* in, uint32_t* out) {
     const f29 x2 = dc_ld29(in + 37), y2 = dc_ld29(in + 46);
     dc_stj(out, j29_to(x29_to_j29(x29_madd(p, x2, y2))));
     dc_stj(out + 24, jac_add_aff(j29_to(x29_to_j29(p)), g1a{f29_to_fp(x2), f29_to_fp(y2), false}));
+  }
+}
+
+// ---- the fused G2 formulas of dev/g2x29.h and dev/g2lines29.h against the
+// 32-bit ones of dev/pairing.h and dev/curve.h (tests/test_gpu_g2_fused.py), a
+// table of its own as DC_G1_OPS.  Operands are raw 29-bit limbs (an Fp2 value:
+// c0 then c1, 18 words); results are canonical 32-bit Montgomery words (an Fp2
+// value: 16 words).
+//   g2f_dbl   in: T = X Y Z, yP, xP.  out: the new T and the three evaluated
+//             coefficients c0 c3 c4 of g2l_dbl (96 words), then dbl_step_inl's
+//             T and its coefficients times yP, xP, 1 (96 words).
+//   g2f_add   in: T, Qx Qy, yP, xP.  out: as g2f_dbl, for g2l_add / add_step_inl.
+//   g2f_xmadd in: the accumulator X Y ZZ ZZZ, its infinity flag, x2 y2.  out:
+//             x2q_madd's sum as a 32-bit Jacobian point (48 words; of the
+//             accumulator when the doubling flag came back), jac_add_aff's on
+//             the same operands (48 words), the doubling flag.
+// A step's new T is the reference's as a homogeneous projective point, and a
+// line is the reference's times one factor in Fp.
+#define DC_G2_OPS(X) X(g2f_dbl, 72, 192) X(g2f_add, 108, 192) X(g2f_xmadd, 109, 97)
+
+enum DcG2Op : int {
+#define DC_X(name, nin, nout) DC_##name,
+  DC_G2_OPS(DC_X)
+#undef DC_X
+  DC_G2_OP_COUNT
+};
+inline const DcInfo* dc_g2_table() {
+  static const DcInfo t[DC_G2_OP_COUNT] = {
+#define DC_X(name, nin, nout) {#name, nin, nout},
+      DC_G2_OPS(DC_X)
+#undef DC_X
+  };
+  return t;
+}
+FTS_HD q2 dc_ldq(const uint32_t* in) { return {dc_ld29(in), dc_ld29(in + 9)}; }
+FTS_HD void dc_st2(uint32_t* out, const fp2& a) {
+  dc_st8(out, a.c0);
+  dc_st8(out + 8, a.c1);
+}
+template <int OP>
+FTS_HD void dc_g2_apply(const uint32_t* in, uint32_t* out) {
+  if constexpr (OP == DC_g2f_dbl || OP == DC_g2f_add) {
+    constexpr int o = OP == DC_g2f_add ? 36 : 0;  // Qx Qy sit between T and P
+    q2 X = dc_ldq(in), Y = dc_ldq(in + 18), Z = dc_ldq(in + 36);
+    const f29 yP = dc_ld29(in + 54 + o), xP = dc_ld29(in + 63 + o);
+    g2p T = {q2_to_fp2(X), q2_to_fp2(Y), q2_to_fp2(Z)};
+    auto emit = [&](int c, const q2& v) { dc_st2(out + 48 + 16 * c, q2_to_fp2(v)); };
+    LineCoef ref;
+    if constexpr (OP == DC_g2f_add) {
+      const q2 Qx = dc_ldq(in + 54), Qy = dc_ldq(in + 72);
+      g2l_add(X, Y, Z, Qx, Qy, g2l_pmults(yP, xP), emit);
+      ref = add_step_inl(T, g2a{q2_to_fp2(Qx), q2_to_fp2(Qy), false});
+    } else {
+      g2l_dbl(X, Y, Z, g2l_pmults(yP, xP), emit);
+      ref = dbl_step_inl(T);
+    }
+    dc_st2(out, q2_to_fp2(X));
+    dc_st2(out + 16, q2_to_fp2(Y));
+    dc_st2(out + 32, q2_to_fp2(Z));
+    dc_st2(out + 96, T.x);
+    dc_st2(out + 112, T.y);
+    dc_st2(out + 128, T.z);
+    dc_st2(out + 144, f2_mul_fp(ref.r0, f29_to_fp(yP)));
+    dc_st2(out + 160, f2_mul_fp(ref.r1, f29_to_fp(xP)));
+    dc_st2(out + 176, ref.r2);
+  } else {
+    static_assert(OP == DC_g2f_xmadd, "dc_g2_apply: op without a branch");
+    const x2q p = {dc_ldq(in), dc_ldq(in + 18), dc_ldq(in + 36), dc_ldq(in + 54), in[72] != 0};
+    const q2 x2 = dc_ldq(in + 73), y2 = dc_ldq(in + 91);
+    bool dbl = false;
+    const x2q s = x2q_madd(p, x2, y2, &dbl);
+    const g2j a = x2q_to_g2j(dbl ? p : s), b = jac_add_aff(x2q_to_g2j(p), g2a{q2_to_fp2(x2), q2_to_fp2(y2), false});
+    dc_st2(out, a.x);
+    dc_st2(out + 16, a.y);
+    dc_st2(out + 32, a.z);
+    dc_st2(out + 48, b.x);
+    dc_st2(out + 64, b.y);
+    dc_st2(out + 80, b.z);
+    out[96] = dbl ? 1u : 0u;
   }
 }
 
