@@ -27,6 +27,7 @@ LIB = os.path.join(HERE, "zkatdlog", "_lib", "libftsamd.so")
 MADPEAK = os.path.join(HERE, "zkatdlog", "_lib", "libftsmadpeak.so")
 FPCHECK = os.path.join(HERE, "zkatdlog", "_lib", "libftsfpcheck.so")
 DEVCHECK = os.path.join(HERE, "zkatdlog", "_lib", "libftsdevcheck.so")  # tests: device primitive conformance
+DEVPAIR = os.path.join(HERE, "zkatdlog", "_lib", "libftsdevpair.so")  # tests: the pairing stage on described jobs
 CALLERS = os.path.join(HERE, "zkatdlog", "_lib", "libftscallers.so")  # bench: closed-loop n=1 callers
 ARCH = os.environ.get("FTS_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -120,13 +121,22 @@ def build(jobs=8, force=False, verbose=True):
         if r.returncode != 0:
             raise RuntimeError("link failed:\n%s\n%s%s" % (" ".join(cmd), r.stdout, r.stderr))
     tool_time = max(hdr_time, newest(glob.glob(os.path.join(CSRC, "tools", "*.h"))))
-    for src, out in ((os.path.join(CSRC, "tools", "madpeak.hip"), MADPEAK),
-                     (os.path.join(CSRC, "tools", "fpcheck.hip"), FPCHECK),
-                     (os.path.join(CSRC, "tools", "devcheck.hip"), DEVCHECK)):
+    def build_tool(pair):
+        src, out = pair
         if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), tool_time):
             r = subprocess.run([HIPCC] + FLAGS + ["-shared", src, "-o", out], capture_output=True, text=True)
             if r.returncode != 0:
-                raise RuntimeError("tool build failed:\n" + r.stderr)
+                return "tool build failed:\n" + r.stderr
+        return None
+
+    # side by side: devcheck.hip and devpair.hip each take minutes (they hold the G1 / G2 and the pairing kernels)
+    with ThreadPoolExecutor(max_workers=jobs) as ex:
+        errs = [e for e in ex.map(build_tool, ((os.path.join(CSRC, "tools", "madpeak.hip"), MADPEAK),
+                                               (os.path.join(CSRC, "tools", "fpcheck.hip"), FPCHECK),
+                                               (os.path.join(CSRC, "tools", "devcheck.hip"), DEVCHECK),
+                                               (os.path.join(CSRC, "tools", "devpair.hip"), DEVPAIR))) if e]
+    if errs:
+        raise RuntimeError("\n".join(errs))
     src = os.path.join(CSRC, "tools", "callers.cpp")
     if force or not os.path.exists(CALLERS) or os.path.getmtime(CALLERS) < max(os.path.getmtime(src),
                                                                                os.path.getmtime(LIB)):

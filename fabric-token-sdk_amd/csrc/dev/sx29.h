@@ -12,8 +12,21 @@
 //     per column, 9 limb products each: 108 x 2^56) plus the reduction's
 //     multiples of p (9 x 2^56) stay below 2^63;
 //   - one Montgomery reduction per sum with balanced digits m_k (|m_k| <= 2^28)
-//     against the balanced limbs of p, which returns a balanced value
-//     |v| < 12 (p/2)^2 / 2^261 + p/2 < 0.52 p directly -- no final subtraction;
+//     against the balanced limbs of p, which returns balanced limbs 0..7 and
+//     |v| <= |sum| / 2^261 + (p/2)(1 + 2^-28) directly -- no final subtraction.
+//     In units of p, with p / 2^261 < 1 / 168.9, a sum of field products of
+//     operands within a and b is within 1/2 + (number of products) a b / 168.9.
+//     Twelve plain products of values of p/2 would stay below 0.52 p, but a
+//     full Fp12 product wraps: its multiplicands xi b_j are up to 10 |b| (lane
+//     0: 2 + 10 x 10 = 102 products of |a| |b|), so sq_mul returns up to
+//     1/2 + 102 |a| |b| / 168.9 -- 0.663 p for operands of 0.52 p, and measured
+//     0.552 p (tests/test_sx_ops.py test_full_product_exceeds_half_p).  Nothing
+//     needs 0.52 p: a value is an operand as long as its limb 8 fits the column
+//     budget (|limb 8| <= 2^28 after the factor 10 of xi: |v| <= 8 p) and, where
+//     it enters f29_lin4, |limb 8| < 2^22 (|v| <= 1.3 p).  The routines below
+//     take operands within 1 p unless they say otherwise; "Value bounds of the
+//     final exponentiation" (below sq_fc_hard) follows every chain: no value
+//     there exceeds 0.88 p;
 //   - xi a, 3 r -/+ 2 a and the other small linear maps are evaluated in 64-bit
 //     limb sweeps together with one quotient-estimate reduction (f29_lin2).
 // The one Fp12 inversion (sx_inv, once per job) runs in the 8 x 32-bit code and
@@ -216,7 +229,9 @@ FTS_HD q2 sq_pub(const X& x, int base, const q2& v_) {
   return v;
 }
 
-// c = a * b, b published in SX_B / SX_BX (as sx_mul)
+// c = a * b, b published in SX_B / SX_BX (as sx_mul).  Operands within 1 p;
+// |c| <= 1/2 + 102 |a| |b| / 168.9 (lane 0: a_0 b_0 + xi (a_1 b_5 + ... + a_5
+// b_1), two field products per Fp2 product and component, xi b_j <= 10 |b|)
 template <class X>
 FTS_HD q2 sq_mul(X x, q2 a) {
   x.put(SX_A + x.k, a);
@@ -536,6 +551,26 @@ FTS_HD fp2 sq_fc_hard(const X& x, const P& pk) {
   res = sq_mulv(x, res, sq_frob3(k, sq_mulv(x, B, sq_conj(k, pk.get(0)))));
   return q2_to_fp2(res);
 }
+// Value bounds of the final exponentiation, in units of p.  M(a, b) = 1/2 +
+// 102 a b / 168.9 bounds a full product (sq_mul), L = 1/2 + 2^-13.4 a value
+// out of f29_lin2 / f29_lin4 (q2_from_fp2, sq_cyc_sqr), F(a) = 1/2 + 2 a (1/2)
+// / 168.9 <= 0.506 a Frobenius map (one Fp2 product by a constant) of a <= 1.
+//   easy part: F <= L; d = M(L, L) = 0.652; tk: two Fp2 products of d and
+//     xi d, <= 0.61; inv6 = one Fp2 product <= 0.51; f^-1 = M(L, 0.51) = 0.66;
+//     m0 = M(L, 0.66) = 0.70; m = M(0.506, 0.70) = 0.72.
+//   sq_expt of a <= 0.72: a^2 = L; a^3 = M(L, 0.72) = 0.72, a^5, a^7 likewise;
+//     a turn is r = L (sq_cyc_sqr), then M(L, 0.72) = 0.72: the result <= 0.72.
+//   sq_fexp_hard_exact from four values <= 0.72: y6^2 = L; t0 = M(L, 0.72) =
+//     0.72, t0 y5 = M(0.72, 0.72) = 0.82; t1 = M(0.72, 0.82) = 0.86, the largest
+//     value of the chain, squared by sq_cyc_sqr (L); t0 y2 = M(0.82, 0.506) =
+//     0.75; y0 <= 0.70; the result M(L, 0.72) = 0.72.
+//   Fuentes-Castaneda: a6 = M(L, L) = 0.652; A = M(M(0.652, 0.72), 0.72) =
+//     0.85; A b = M(0.85, 0.72) = 0.87, times t: M(0.87, 0.72) = 0.88, the
+//     largest; B = M(0.85, L) = 0.76, B conj(t) = M(0.76, 0.72) = 0.83; the
+//     products that build the result have a factor F(.) <= 0.506 and stay
+//     below 0.77.
+// Every operand is therefore within 1 p, sq_cyc_sqr's within its f29_lin4's
+// 1.3 p, and no limb 8 comes near the column budget.
 template <class X, class P>
 FTS_HD fp2 sq_final_exp(const X& x, const fp2& f, const P& pk) {
   pk.put(0, sq_fexp_easy(x, f));

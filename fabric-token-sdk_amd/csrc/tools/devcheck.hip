@@ -2,6 +2,14 @@
 // op of tools/devcheck_ops.h as its own kernel, one vector per lane, operands
 // read from and results written to global memory so that nothing folds at
 // compile time.  The host supplies the operands and gets the raw result words.
+// Further sections, each with entry points of its own:
+//   DC_G1_OPS / DC_G2_OPS   the fused G1 and G2 formulas (ftz_devcheck_g1, _g2)
+//   ftz_devcheck_g1_chain, _g1_jobs, _g2_jobs   the G1 and G2 stages as launched
+//   DC_SX_OPS (dev/devcheck_sx.h)   the sextet pairing routines of dev/sx29.h,
+//       six lanes per job in the production prologue: ftz_devcheck_sx_info,
+//       ftz_devcheck_sx (tests/test_gpu_sx_ops.py)
+// The pairing stage itself (k_qlines, k_miller*, launch_fexp on described jobs)
+// is tools/devpair.hip, a shared object of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -473,4 +481,73 @@ extern "C" int ftz_devcheck_g2_jobs(int device, uint32_t n, const uint32_t* jobs
   delete[] hp;
   delete[] hj;
   return ok ? -(int)e : -1000;
+}
+
+// ---- the sextet table (DC_SX_OPS of dev/devcheck_sx.h, tests/test_gpu_sx_ops.py):
+// one kernel per op, launched as the runtime launches its sextet kernels -- 64
+// lanes per workgroup, (n + 9) / 10 workgroups, the prologue of launch.h with
+// the op's slot count and second-operand offset -- so the lane-to-sextet map,
+// the ghost lanes 60..63, the LDS region stride and SyncWave are the production
+// ones.  A lane of a sextet past n runs the last job's program in its own
+// region (as in production) and stores nothing.
+#include "../dev/devcheck_sx.h"
+
+template <int OP, int NIN, int NS, int BOFS, int WAVES>
+__global__ void __launch_bounds__(64, WAVES) k_devcheck_sx(uint32_t n, const uint32_t* in, uint32_t* out,
+                                                          int32_t* park) {
+  SQ_KERNEL_PROLOGUE_B(n, NS, BOFS)
+  const Park pk{park, blockIdx.x * 64 + threadIdx.x, gridDim.x * 64, !ghost_};
+  const q2 r = dc_sx_apply<OP>(x, in + (size_t)jc * NIN, pk);
+  if (valid) dc_sx_stq(out + ((size_t)job_ * 6 + x.k) * 18, r);
+}
+
+// the table: returns the number of ops; for 0 <= op < that, the name, the words
+// read per job, the words written per job (108) and the LDS layout
+extern "C" int ftz_devcheck_sx_info(int op, char name[32], uint32_t* nin, uint32_t* nout, uint32_t* slots,
+                                    uint32_t* bofs) {
+  if (op >= 0 && op < DC_SX_OP_COUNT) {
+    const DcSxInfo& e = dc_sx_table()[op];
+    strncpy(name, e.name, 31);
+    name[31] = 0;
+    *nin = e.nin;
+    *nout = DC_SX_OUT;
+    *slots = e.slots;
+    *bofs = e.bofs;
+  }
+  return DC_SX_OP_COUNT;
+}
+
+// Runs op on n jobs (in: n * nin words).  out holds 108 words for every sextet
+// of every workgroup, the idle ones of the last workgroup included: filled with
+// 0xA5A5A5A5 before the launch and copied back whole.  The park planes
+// (fexp_park_bytes(n)) are scratch.  Returns 0, -(HIP error code) or -1000.
+extern "C" int ftz_devcheck_sx(int device, int op, uint32_t n, const uint32_t* in, uint32_t* out) {
+  if (op < 0 || op >= DC_SX_OP_COUNT || n == 0 || n > 65536 || !in || !out) return -1000;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return -(int)e;
+  const DcSxInfo& info = dc_sx_table()[op];
+  const uint32_t blocks = (n + SX_JOBS_PER_WAVE - 1) / SX_JOBS_PER_WAVE;
+  const size_t in_bytes = (size_t)n * info.nin * 4, out_bytes = (size_t)blocks * SX_JOBS_PER_WAVE * DC_SX_OUT * 4;
+  uint32_t *din = nullptr, *dout = nullptr;
+  int32_t* dpark = nullptr;
+  if ((e = hipMalloc(&din, in_bytes)) == hipSuccess && (e = hipMalloc(&dout, out_bytes)) == hipSuccess &&
+      (e = hipMalloc(&dpark, fexp_park_bytes(n))) == hipSuccess &&
+      (e = hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice)) == hipSuccess &&
+      (e = hipMemset(dpark, DC_SENTINEL & 0xFF, fexp_park_bytes(n))) == hipSuccess &&
+      (e = hipMemset(dout, DC_SENTINEL & 0xFF, out_bytes)) == hipSuccess) {
+    switch (op) {
+#define DC_X(name, nin, ns, bofs, waves)                                                          \
+  case DC_##name:                                                                                 \
+    k_devcheck_sx<DC_##name, nin, ns, bofs, waves><<<blocks, 64>>>(n, din, dout, dpark); \
+    break;
+      DC_SX_OPS(DC_X)
+#undef DC_X
+    }
+    if ((e = hipGetLastError()) == hipSuccess && (e = hipDeviceSynchronize()) == hipSuccess)
+      e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  (void)hipFree(dpark);
+  return -(int)e;
 }

@@ -227,6 +227,18 @@ int main(int argc, char** argv) {
       }
       for (int n = 1; n <= 6; n++) prod(n, a, b, 1);
     }
+    // the full product's stated contract (sx29.h, sq_mul): operands of 1 p, five of the six
+    // multiplicands the wrapped xi b_j of 10 p (carry-swept: limb 8 holds the excess), worst signs
+    for (int neg = 0; neg < 2; neg++) {
+      q2 a[6], b[6];
+      const int32_t one = 3171407, ten = 10 * 3171407;
+      for (int t = 0; t < 6; t++) {
+        const int32_t m = t ? ten : one;
+        a[t] = {corner(B28, 0, one), corner(B28, 0, one)};
+        b[t] = {corner(B28, neg ? 0xFF : 0, neg ? -m : m), corner(B28, neg ? 0 : 0xFF, neg ? m : -m)};
+      }
+      for (int n = 1; n <= 6; n++) prod(n, a, b, 1);
+    }
   }
   for (int i = 0; i < n_rand / 3; i++) {
     q2 a[6], b[6];

@@ -14,6 +14,7 @@
 #include "../../fabric-token-sdk_amd/csrc/dev/sx29.h"
 #include "g2l29.h"
 #include "../../fabric-token-sdk_amd/csrc/dev/g2lines29.h"
+#include "../../fabric-token-sdk_amd/csrc/dev/devcheck_sx.h"
 
 using namespace fts;
 
@@ -41,20 +42,34 @@ void run6(const std::function<void(const SxH&)>& body) {
   pthread_barrier_destroy(&b);
 }
 
-typedef Sq<SyncHost> SqH;
-void run6q(const std::function<void(const SqH&)>& body) {
-  std::vector<Q2Slot> slots(SX_SLOTS_FEXP);
-  memset(slots.data(), 0xA5, slots.size() * sizeof(Q2Slot));
+// the same for the carry-free context, in a layout of `slots` slots with the
+// second operand's group at BOFS
+template <int BOFS>
+void run6qb(int slots, const std::function<void(const Sq<SyncHost, BOFS>&)>& body) {
+  std::vector<Q2Slot> region(slots);
+  memset(region.data(), 0xA5, region.size() * sizeof(Q2Slot));
   pthread_barrier_t b;
   pthread_barrier_init(&b, nullptr, 6);
   std::vector<std::thread> th;
   for (int k = 0; k < 6; k++)
     th.emplace_back([&, k] {
-      SqH x{k, slots.data(), true, {&b}};
+      Sq<SyncHost, BOFS> x{k, region.data(), true, {&b}};
       body(x);
     });
   for (auto& t : th) t.join();
   pthread_barrier_destroy(&b);
+}
+typedef Sq<SyncHost> SqH;  // the 30-slot layout
+void run6q(const std::function<void(const SqH&)>& body) { run6qb<SX_B>(SX_SLOTS_FEXP, body); }
+
+// one job of an op of csrc/dev/devcheck_sx.h (sxe_sx_ops, below)
+template <int OP, int BOFS>
+void sxe_sx_job(int slots, const uint32_t* in, uint32_t* out) {
+  std::vector<int32_t> park(6 * FEXP_PARK_SLOTS * 18, (int32_t)0xA5A5A5A5);
+  run6qb<BOFS>(slots, [&](const Sq<SyncHost, BOFS>& x) {
+    Park pk{park.data(), (uint32_t)x.k, 6, true};
+    dc_sx_stq(out + 18 * x.k, dc_sx_apply<OP>(x, in, pk));
+  });
 }
 
 uint32_t xs(uint32_t& s) {
@@ -449,6 +464,36 @@ int sxe_g2lines29(const uint8_t* bases, const uint8_t* p2, const uint8_t* scalar
   memcpy(gt, out[1], 384);
   if (memcmp(out[0], out[2], 384)) return 4;
   return memcmp(out[0], out[1], 384) ? 2 : 0;
+}
+
+// The sextet op table of csrc/dev/devcheck_sx.h on the emulation
+// (tests/test_sx_ops.py): the words the device tool reads and writes, one job
+// at a time on six threads, in the op's own slot layout.  sxe_sx_info is
+// ftz_devcheck_sx_info's twin; sxe_sx_ops writes 108 words per job.
+int sxe_sx_info(int op, char name[32], uint32_t* nin, uint32_t* nout, uint32_t* slots, uint32_t* bofs) {
+  if (op >= 0 && op < DC_SX_OP_COUNT) {
+    const DcSxInfo& e = dc_sx_table()[op];
+    strncpy(name, e.name, 31);
+    name[31] = 0;
+    *nin = e.nin;
+    *nout = DC_SX_OUT;
+    *slots = e.slots;
+    *bofs = e.bofs;
+  }
+  return DC_SX_OP_COUNT;
+}
+
+int sxe_sx_ops(int op, uint32_t n, const uint32_t* in, uint32_t* out) {
+  if (op < 0 || op >= DC_SX_OP_COUNT || !in || !out) return -1000;
+  for (uint32_t j = 0; j < n; j++) switch (op) {
+#define DC_X(name, nin, ns, bofs, waves)                                                        \
+  case DC_##name:                                                                               \
+    sxe_sx_job<DC_##name, bofs>(ns, in + (size_t)j * (nin), out + (size_t)j * DC_SX_OUT); \
+    break;
+      DC_SX_OPS(DC_X)
+#undef DC_X
+    }
+  return 0;
 }
 
 }  // extern "C"
